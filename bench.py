@@ -8,8 +8,14 @@ with SURVEY.md §8d's pinned hyper-parameters (Tanh 64-64 actor/critic, Adam 3e-
 lambda .95, eps_clip .2, vf_coef .25, ent_coef 0, max_grad_norm .5, rew_norm on,
 norm_adv on, VectorEnvNormObs on, 32 minibatches, repeat 4).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+the legs that take runs of their own after the timed region: the CPU baseline
+(cpu_baseline) and, data parallel, the per-kind collective timing
+(data_parallel.collective_timing); without it both are null.  --dump-outputs DIR writes what
+the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs).
 
 Multi-GPU = env sharding (weak scaling: every rank runs envs x T of its own), RCCL
 all-reduce of gradients / advantage moments / ret_rms partials.  Rank 0 prints one JSON line.
@@ -74,6 +80,15 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=None,
                     help="T' of the bounded CPU-baseline sample (envs x T')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed "
+                         "steps: the CPU baseline (unless --no-cpu-baseline) and, data "
+                         "parallel, the timing of each collective kind at its payload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its "
+                         "caller (collect statistics, update losses, the updated parameters "
+                         "and statistics, a fixed seeded sample of the collected buffer rows) "
+                         "as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--act-coef", type=float, default=0.0,
                     help="diagnostic: the action-coupled synthetic env (obs = box + c * action, "
                          "not 2^-23-quantised): the fused collect step's general path (env "
@@ -104,6 +119,8 @@ def parse():
                          "< 65536 rows (PPOPolicy default); on at the headline shape measured "
                          "~5 %% slower per update than eager launches")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     defaults = dict(humanoid=(4096, 2048, 376, 17, 256, 1000),
                     small=(512, 128, 17, 6, 128, 1000),
                     atari=(1024, 256, 0, 6, 16, 256),
@@ -173,6 +190,64 @@ def gae_pmc_traffic(E: int, T: int):
             return d["traffic_bytes"], f"{os.path.relpath(pmc, ROOT)} (gae.hip sha256 {sha[:12]})"
     return None, (f"stale: no profiles/r*_gae_pmc.json measured on this gae.hip "
                   f"(sha256 {sha[:12]}); re-run tools/pmc_gae.py")
+
+
+DUMP_SAMPLE_ROWS = 4096       # buffer rows kept by --dump-outputs (fixed seeded sample)
+DUMP_MAX_BYTES = 64 << 20     # everything --dump-outputs writes stays below this
+DUMP_KEY_BYTES = 16 << 20     # ... and one sampled buffer key below this
+
+
+def dump_outputs(out_dir, last, coll, policy, buf):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy
+    (floats as float32 / float64, integers and flags as float64):
+
+      collect_*   Collector.collect's statistics (n/ep, n/st, episode returns and lengths)
+      update_*    PPOPolicy.update's loss lists (one entry per minibatch)
+      param_*     the parameters that update left in the policy
+      obs_rms_* / ret_rms_*  the running statistics the step updated
+      buffer_*    the rows the step collected -- reset_buffer rewinds the ring and leaves the
+                  storage as it is --: DUMP_SAMPLE_ROWS rows drawn once by a generator of
+                  its own (seed 0; the draw is buffer_rows), fewer for wide rows
+
+    Seeds, shapes and hyper-parameters are fixed by the arguments, so two builds run with the
+    same arguments are given identical inputs and their files compare name for name."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def put(name, x):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x)
+        arrays[name] = x.astype(np.float32 if x.dtype == np.float32 else np.float64)
+
+    for k in ("n/ep", "n/st", "rews", "lens"):
+        put("collect_" + k.replace("/", "_"), last["collect"][k])
+    for k, v in last["update"].items():
+        put("update_" + k.replace("/", "_"), v)
+    for k, p in policy.named_parameters():
+        put("param_" + k, p)
+    norm = getattr(coll, "_norm", None)
+    for tag, rms in (("obs_rms", getattr(norm, "obs_rms", None)),
+                     ("ret_rms", getattr(policy, "ret_rms", None))):
+        if rms is not None and hasattr(rms, "mean"):
+            put(tag + "_mean", rms.mean)
+            put(tag + "_var", rms.var)
+    m = buf.maxsize
+    rows = min(m, DUMP_SAMPLE_ROWS)
+    keys = [k for k in ("obs", "act", "rew", "terminated", "truncated") if k in buf._meta.keys()]
+    for k in keys:
+        per_row = 4 * max(int(np.prod(buf._meta[k].shape[1:])), 1)
+        rows = max(1, min(rows, DUMP_KEY_BYTES // per_row))
+    pick = np.sort(np.random.default_rng(0).choice(m, size=rows, replace=False))
+    put("buffer_rows", pick)
+    pick_t = torch.as_tensor(pick, device=buf._meta[keys[0]].device)
+    for k in keys:
+        x = buf._meta[k][pick_t]
+        put("buffer_" + k, x.float() if x.dtype == torch.uint8 else x)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def build_atari(args, dev, rank):
@@ -333,13 +408,16 @@ def main():
     pbase.GAE_HOOK = timer
     phase = {"collect": 0.0, "update": 0.0}
 
+    last = {}  # what the latest iteration returned to its caller (--dump-outputs)
+
     def iteration():
         t0 = time.perf_counter()
-        coll.collect(n_step=n)
+        last["collect"] = coll.collect(n_step=n)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        policy.update(0, buf, batch_size=args.batch_size or n // args.minibatches,
-                      repeat=args.repeat)
+        last["update"] = policy.update(0, buf,
+                                       batch_size=args.batch_size or n // args.minibatches,
+                                       repeat=args.repeat)
         coll.reset_buffer(keep_statistics=True)
         torch.cuda.synchronize()
         phase["collect"] += t1 - t0
@@ -372,12 +450,14 @@ def main():
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, coll, policy, buf)
     dp_report = None
     if distributed:
         # N > 1 self-report (rank-collective; every rank takes part): per-iteration counts of
-        # each collective kind in the timed region, each kind timed at its payload, the
-        # collect / update split of every rank, and replica consistency (parameter hash
-        # all-reduced MAX == MIN)
+        # each collective kind in the timed region, each kind timed at its payload (--full:
+        # runs of its own), the collect / update split of every rank, and replica consistency
+        # (parameter hash all-reduced MAX == MIN)
         import torch.distributed as dist
         calls = {k: v / args.steps for k, v in sorted(tdist.LOG.calls.items())}
         split = torch.tensor([phase["collect"] / args.steps, phase["update"] / args.steps],
@@ -388,7 +468,7 @@ def main():
         hmax, hmin = h.clone(), h.clone()
         dist.all_reduce(hmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(hmin, op=dist.ReduceOp.MIN)
-        probe = tdist.probe_collectives(tdist.default_dp())
+        probe = tdist.probe_collectives(tdist.default_dp()) if args.full else None
         dp_report = {
             "rccl_world_size": dist.get_world_size(),
             "collectives_per_iter": calls,
@@ -406,7 +486,7 @@ def main():
     traffic, traffic_note = gae_pmc_traffic(E, T)
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import cpu_port
             threads = min(16, os.cpu_count() or 1)
             v, dt = cpu_port.run_iteration(E, args.cpu_steps, D, A, repeat=args.repeat,

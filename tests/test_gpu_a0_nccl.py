@@ -32,7 +32,7 @@ def test_bench_force_dp_one_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node",
            "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--envs", "512", "--T", "128", "--no-cpu-baseline", "--force-dp"]
+           "--envs", "512", "--T", "128", "--no-cpu-baseline", "--force-dp", "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
