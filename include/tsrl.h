@@ -180,7 +180,9 @@ int tsrl_rms_norm_rows(const float* x, const uint8_t* mask, int64_t k, int64_t d
  * the rows of x taken by mask (all when NULL); snap_mean / snap_var (nullable, both or none)
  * receive the state after it; then, when x2 is non-NULL, a second update with x2's rows taken
  * by mask2 (the reset rows of the same vector step).  `ticket`: a zero-initialised device word
- * of the statistics object (re-armed by the call).  One thread per column, latency-bound. */
+ * of the statistics object (re-armed by the call).  One thread per column, latency-bound.
+ * dim == 1 is refused (hipErrorInvalidValue): over a [k, 1] array NumPy reduces the contiguous
+ * axis and sums pairwise, which the sequential row-order sums here do not reproduce. */
 int tsrl_rms_exact_update(const float* x, const uint8_t* mask, int64_t k, const float* x2,
                           const uint8_t* mask2, int64_t k2, int64_t dim, float* mean, float* var,
                           double* count, float* snap_mean, float* snap_var,

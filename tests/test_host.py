@@ -142,6 +142,16 @@ def test_device_stats_construct_without_gpu_use():
     assert (s.mean, s.var, s.count) == (0.0, 1.0, 0)
 
 
+def test_exact_device_stats_refuse_one_column():
+    """exact=True promises the reference's bits; over a [k, 1] array NumPy sums pairwise, which
+    the sequential exact kernel does not reproduce, so the object refuses to be built."""
+    from tianshou_amd.utils.statistics import DeviceRunningMeanStd
+    with pytest.raises(ValueError, match="pairwise"):
+        DeviceRunningMeanStd(1, "cpu", exact=True)
+    assert DeviceRunningMeanStd(1, "cpu").dim == 1  # the default path has no such limit
+    assert DeviceRunningMeanStd(2, "cpu", exact=True).exact
+
+
 @pytest.mark.parametrize("n,bs", [(1024, 128), (1000, 128), (1000, 300), (7, 10)])
 def test_sorted_minibatch_permutation_same_sets(n, bs):
     """PPOPolicy.sort_minibatch: each minibatch holds the same rows as Batch.split over the

@@ -398,6 +398,10 @@ extern "C" int tsrl_rms_exact_update(const float* x, const uint8_t* mask, int64_
     TSRL_CHECK_ARG(x && mean && var && count && ticket && dim > 0 && k >= 0 && k2 >= 0 &&
                        (snap_mean == nullptr) == (snap_var == nullptr),
                    "tsrl_rms_exact_update: bad arguments");
+    // a [k, 1] array is contiguous along the reduced axis: NumPy sums it pairwise, which the
+    // sequential row-order chains here do not reproduce
+    TSRL_CHECK_ARG(dim != 1, "tsrl_rms_exact_update: dim == 1 is not the reference's "
+                             "arithmetic (NumPy sums a single column pairwise)");
     const tsrl::exact::Rows b1{x, mask, k};
     const tsrl::exact::Rows b2{x2, mask2, x2 ? k2 : 0};
     const unsigned grid = (unsigned)((dim + tsrl::exact::XC - 1) / tsrl::exact::XC);

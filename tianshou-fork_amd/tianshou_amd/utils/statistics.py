@@ -51,11 +51,17 @@ class DeviceRunningMeanStd:
     relative (f64 moments are more accurate than NumPy's f32 sums).  ``exact=True``: the
     reference's own f32 arithmetic bit for bit (sequential row-order f32 column sums of
     np.mean / np.var, tsrl_rms_exact_update), at the cost of two k-long dependent f32 add
-    chains per column on every update (single process only)."""
+    chains per column on every update (single process only; dim >= 2: NumPy sums a single
+    column pairwise, so ``dim == 1`` with ``exact`` raises ValueError)."""
 
     def __init__(self, dim: int, device, clip_max: Optional[float] = 10.0,
                  epsilon: float = np.finfo(np.float32).eps.item(), exact: bool = False) -> None:
         self.dim = int(dim)
+        if exact and self.dim == 1:
+            raise ValueError(
+                "exact obs_rms needs dim >= 2: over a [k, 1] f32 array np.mean / np.var reduce "
+                "the contiguous axis and sum pairwise, not in the sequential row order the "
+                "exact kernel reproduces, so its result would not be the reference's bits")
         self.device = torch.device(device)
         self.mean_t = torch.zeros(self.dim, dtype=torch.float32, device=self.device)
         self.var_t = torch.ones(self.dim, dtype=torch.float32, device=self.device)
