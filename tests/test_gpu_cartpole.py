@@ -194,3 +194,45 @@ def test_cartpole_learn_graph_equals_eager(golden_dir, dev):
     n_mb = len(split_bounds(int(z["n_step"]), 64, True))
     for i, st in os0["state"].items():
         assert float(st["step"]) == float(os1["state"][i]["step"]) == 8 * n_mb
+
+
+def test_cartpole_learn_graph_capture_failure_falls_back(golden_dir, dev, monkeypatch):
+    """The Categorical learn path when the learn-graph capture fails (simulated on the host:
+    the capture entry raises RuntimeError before torch.cuda.graph is entered): one
+    UserWarning, _graph_failed set, _learn_graph None, no second capture attempt in that or
+    the next learn(), and the same losses and parameters as the graph_learn=False run."""
+    from tianshou_amd.policy import ppo
+    z = np.load(os.path.join(golden_dir, "cartpole.npz"))
+    tries = []
+
+    def failing_capture(graph):
+        tries.append(graph)
+        raise RuntimeError("simulated capture failure")
+
+    monkeypatch.setattr(ppo, "graph_capture", failing_capture)
+    runs = []
+    for graph in (False, None):
+        envs, policy, buf, c = _build(z, dev)
+        policy.graph_learn = graph
+        c.collect(n_step=int(z["n_step"]), random=True)
+        np.random.seed(77)
+        out = []
+        for u in range(2):
+            batch, idx = buf.sample(0)
+            batch = policy.process_fn(batch, buf, idx)
+            if graph is None and u == 0:
+                # the first epoch runs eagerly, the second one tries the capture
+                with pytest.warns(UserWarning, match="learn-graph capture failed"):
+                    out.append(policy.learn(batch, batch_size=64, repeat=4))
+            else:
+                out.append(policy.learn(batch, batch_size=64, repeat=4))
+            assert len(tries) == (1 if graph is None else 0)
+            assert policy._graph_failed == (graph is None) and policy._learn_graph is None
+        assert policy._cat_adam is not None and policy._cat_adam.adam_bound(policy.optim)
+        runs.append((out, {k: v.detach().cpu().numpy() for k, v in policy.state_dict().items()}))
+    (o0, sd0), (o1, sd1) = runs
+    for a, b in zip(o0, o1):
+        for k in a:
+            np.testing.assert_allclose(b[k], a[k], rtol=1e-6, atol=1e-7, err_msg=k)
+    for k in sd0:
+        np.testing.assert_allclose(sd1[k], sd0[k], rtol=1e-6, atol=1e-7, err_msg=k)

@@ -485,6 +485,61 @@ def test_learn_graph_replay_matches_eager(dev):
         assert torch.equal(states[0][k], states[1][k]), k
 
 
+def test_learn_graph_capture_failure_falls_back(dev, monkeypatch):
+    """A learn-graph capture that fails (simulated on the host: the capture entry raises
+    RuntimeError before torch.cuda.graph is entered, so no stream is ever capturing) warns
+    once, sets _graph_failed, leaves _learn_graph None and runs that epoch and every later
+    one eagerly -- a second learn() does not try to capture again -- with losses and
+    parameters bit-identical to a graph_learn=False run."""
+    from tianshou_amd.data import Batch
+    from tianshou_amd.env import Box
+    from tianshou_amd.policy import PPOPolicy
+    from tianshou_amd.policy import ppo
+    from tianshou_amd.utils.models import fixed_std_normal
+    D, A, n = 40, 6, 3000
+    base_a, base_c = _nets(D, A, dev, 21)
+    tries = []
+
+    def failing_capture(graph):
+        tries.append(graph)
+        raise RuntimeError("simulated capture failure")
+
+    monkeypatch.setattr(ppo, "graph_capture", failing_capture)
+    res, states = [], []
+    for graph in (None, False):
+        actor, critic = copy.deepcopy(base_a), copy.deepcopy(base_c)
+        params = list(actor.parameters()) + [p for p in critic.parameters()
+                                             if all(p is not q for q in actor.parameters())]
+        optim = torch.optim.Adam(params, lr=3e-4, fused=True, capturable=True)
+        pol = PPOPolicy(actor, critic, optim, fixed_std_normal, action_space=Box(-1.0, 1.0, (A,)),
+                        max_grad_norm=0.5, vf_coef=0.25, ent_coef=0.01, perm_device=True)
+        pol.graph_learn = graph
+        g = torch.Generator().manual_seed(1)
+        data = dict(obs=torch.randn(n, D, generator=g), act=torch.randn(n, A, generator=g),
+                    logp_old=torch.randn(n, generator=g) * 0.2 - A * 1.2,
+                    adv=torch.randn(n, generator=g), returns=torch.randn(n, generator=g))
+        data["v_s"] = data["returns"] + 0.3 * torch.randn(n, generator=g)
+        batch = Batch(**{k: v.to(dev) for k, v in data.items()})
+        torch.manual_seed(3)
+        if graph is None:
+            with pytest.warns(UserWarning, match="learn-graph capture failed"):
+                out = [pol.learn(batch, batch_size=512, repeat=2)]
+            assert len(tries) == 1
+        else:
+            out = [pol.learn(batch, batch_size=512, repeat=2)]
+        assert pol._graph_failed == (graph is None) and pol._learn_graph is None
+        out.append(pol.learn(batch, batch_size=512, repeat=2))
+        assert len(tries) == 1  # neither the eager policy nor the failed one captures again
+        assert pol._graph_failed == (graph is None) and pol._learn_graph is None
+        res.append(out)
+        states.append({k: v.detach().cpu() for k, v in pol.state_dict().items()})
+    for a, b in zip(res[0], res[1]):
+        for k in a:
+            assert a[k] == b[k], k
+    for k in states[0]:
+        assert torch.equal(states[0][k], states[1][k]), k
+
+
 @pytest.mark.parametrize("D,n,with_act,gathered", [
     (376, 2 * 262144 + 77, True, False), (376, 5000, False, False), (376, 3001, True, True),
     (17, 1000, True, False), (40, 257, True, True)])

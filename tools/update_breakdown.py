@@ -61,7 +61,7 @@ def main():
         print(f"{k:12s} {v / a.iters * 1e3:8.1f} ms", flush=True)
     print("graph learn:", pol._learn_graph is not None)
     opt = pol.optim
-    print("ready:", pol._graph_ready(), "graph_learn", pol.graph_learn, "dp", pol.dp.active,
+    print("ready:", pol._graph_ready(()), "graph_learn", pol.graph_learn, "dp", pol.dp.active,
           "recompute", pol._recompute_adv, "capturable", opt.defaults.get("capturable"),
           "nstate", len(opt.state),
           "missing", sum(1 for g in opt.param_groups for p in g["params"] if p not in opt.state))
