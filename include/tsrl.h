@@ -206,7 +206,7 @@ int tsrl_rms_exact_update(const float* x, const uint8_t* mask, int64_t k, const 
  *   with reset_mean / reset_var (collector.py:342-361, the obs of the new episode).
  * rel_next (nullable, with rel_dev): receives (*rel_dev + 1) % ring_size -- the cursor of the
  *   next step in the other slot of a ping-pong pair (graph-captured steps alternate the two
- *   slots), replacing a separate tsrl_ring_advance launch.
+ *   slots), so the cursor needs no launch of its own.
  * ------------------------------------------------------------------------------- */
 typedef struct tsrl_add_args {
     const int64_t* ids;      /* [k] env ids or NULL (identity) */
@@ -218,8 +218,8 @@ typedef struct tsrl_add_args {
     int64_t uniform_rel;     /* every env at the same sub-buffer index (n_step collect) */
     int64_t uniform_next;
     const int64_t* rel_dev;  /* non-NULL: the uniform index is read from device memory (a
-                                HIP-graph-replayable step; advance it with
-                                tsrl_ring_advance), next = (rel + 1) % ring_size */
+                                HIP-graph-replayable step; rel_next advances it),
+                                next = (rel + 1) % ring_size */
     int64_t ring_size;
     /* row payloads */
     const void* obs_src; void* obs_dst; int64_t obs_row_bytes;
@@ -359,8 +359,6 @@ int tsrl_rms_exact_stats_n(int nsteps, const float* const* x, const float* const
                            void* const* stats, void* stream);
 /* The largest nsteps tsrl_rms_exact_stats_n accepts (the Collector clamps its exact_group). */
 int tsrl_rms_exact_stats_max_steps(void);
-/* *rel_dev = (*rel_dev + 1) % ring_size (device-side ring cursor for graph-captured steps). */
-int tsrl_ring_advance(int64_t* rel_dev, int64_t ring_size, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Episode-aware index stepping and frame stacking of a VectorReplayBuffer whose `num`
@@ -581,9 +579,9 @@ int tsrl_cat_gumbel_argmax(const float* logits, const float* u, int64_t n, int64
  *
  * tsrl_mlp_l1_fwd: H1 = act(X[idx] W^T + b) for the stacked first layers (Wa, ba: actor
  *   [64, D]; Wc, bc: critic [64, D]) -> 128 features per row.  frag_out = 1 writes the MFMA
- *   fragment layout consumed by tsrl_ppo_tail (tsrl_mlp_frag_floats(n) floats); 0 writes
+ *   fragment layout consumed by tsrl_ppo_tail_stage (tsrl_mlp_frag_floats(n) floats); 0 writes
  *   row-major [n, 128].  D and ldx multiples of 4, 16-byte aligned X / W / out.
- * tsrl_ppo_tail: layers 2-3 of both nets, the PPO loss of tsrl_ppo_gauss_fwd_bwd and the
+ * tsrl_ppo_tail_stage: layers 2-3 of both nets, the PPO loss of tsrl_ppo_gauss_fwd_bwd and the
  *   backward to dZ1 [n, 128] (row-major), writing the layer-2/3 parameter gradients of the
  *   mean loss and the loss sums [4 + A] (layout of tsrl_ppo_gauss_finalize's input).
  * tsrl_mlp_dw: first-layer gradients dW = dZ1^T X[idx], db = column sums of dZ1.  Row
@@ -617,29 +615,15 @@ int tsrl_mlp_l1_fwd_x6(const float* X, int64_t ldx, const int64_t* idx, int64_t 
                        const void* wsplit, const float* ba, const float* bc, int act_tanh,
                        float* out, int frag_out, void* stream);
 int64_t tsrl_ppo_tail_workspace_bytes(int64_t n);
-int tsrl_ppo_tail(const float* h1frag, int64_t n, const int64_t* idx,
-                  const tsrl_tail_weights* w, int64_t act_dim, const float* act,
-                  const float* logp_old, const float* adv, const float* ret, const float* v_s,
-                  const double* adv_sums, tsrl_ppo_params p, float* dz1,
-                  const tsrl_tail_grads* grads, double* sums, void* workspace,
-                  int64_t ws_bytes, void* stream);
-/* tsrl_ppo_tail_fin: tsrl_ppo_tail followed, inside its reduction launch, by the loss
- * finalisation of tsrl_ppo_gauss_finalize on the reduced sums (losses[4] = loss, clip, vf,
- * entropy; grad_log_std[act_dim]): the single-process minibatch (no all-reduce of the sums
- * between the two), one launch fewer per minibatch. */
-int tsrl_ppo_tail_fin(const float* h1frag, int64_t n, const int64_t* idx,
-                      const tsrl_tail_weights* w, int64_t act_dim, const float* act,
-                      const float* logp_old, const float* adv, const float* ret, const float* v_s,
-                      const double* adv_sums, tsrl_ppo_params p, float* dz1,
-                      const tsrl_tail_grads* grads, double* sums, void* workspace,
-                      int64_t ws_bytes, const float* log_std, float* losses,
-                      float* grad_log_std, void* stream);
-/* tsrl_ppo_tail_stage: the same work in two stages so the caller can run the reduction on a
- * second stream beside tsrl_mlp_dw (both only read what the tail kernels wrote):
- * stages & 1 = the actor and critic tail kernels, stages & 2 = the reduction (with the loss
- * finalisation when log_std/losses/grad_log_std are given — all three or none), 3 = both;
+/* tsrl_ppo_tail_stage runs in stages so the caller can run the reduction on a second stream
+ * beside tsrl_mlp_dw (both only read what the tail kernels wrote):
+ * stages & 1 = the actor and critic tail kernels, stages & 2 = the reduction, 3 = both;
  * stages & 4 / & 8 = the actor's / the critic's tail kernel alone (disjoint outputs: two
- * streams may run them concurrently, both before the reduction). */
+ * streams may run them concurrently, both before the reduction).
+ * With log_std/losses/grad_log_std given (all three or none) the reduction launch also does
+ * the loss finalisation of tsrl_ppo_gauss_finalize on the reduced sums (losses[4] = loss,
+ * clip, vf, entropy; grad_log_std[act_dim]): the single-process minibatch (no all-reduce of
+ * the sums between the two), one launch fewer per minibatch. */
 int tsrl_ppo_tail_stage(const float* h1frag, int64_t n, const int64_t* idx,
                         const tsrl_tail_weights* w, int64_t act_dim, const float* act,
                         const float* logp_old, const float* adv, const float* ret,

@@ -30,9 +30,73 @@ CASES = [
 ]
 
 
+# Directed rows: overwritten over the first rows of a random minibatch so that every branch of
+# the shared surrogate / value-loss functions (csrc/ppo_loss.h) is taken deterministically.
+# B = 257 rows through an index into 294 stored rows: two blocks, a ragged last one.
+DIRECTED = dict(eps_clip=0.25, dual_clip=3.0, value_clip=True, norm_adv=False)
+DIRECTED_B, DIRECTED_N = 257, 294
+# (v, v_s, ret) with eps_clip = 0.25: v - v_s exactly +eps_clip and -eps_clip (clamp passes the
+# gradient on the closed interval), an exact tie vf1 == vf2, the unclipped branch wins, the
+# clipped branch wins out of range (gradient exactly 0).
+VALUE_ROWS = [(0.75, 0.5, 1.0), (0.25, 0.5, 1.0), (0.5, 0.5, 1.0), (1.0, 0.5, 0.0),
+              (1.0, 0.5, 1.2)]
+# d(vf)/d(v) of VALUE_ROWS (torch's semantics, checked on the CPU): the gradient of the mean
+# loss w.r.t. value times B / vf_coef
+VALUE_ROWS_DV = [-0.5, -1.5, -1.0, 2.0, 0.0]
+# (log ratio, advantage) with lo, hi = 0.75, 1.25 and dual_clip = 3: ratio == 1 exactly (the
+# tie surr1 == surr2) for both signs of the advantage, the ratio above hi, above dual_clip
+# (ratio > 3 with an < 0 takes clip1 < dual * an) and below lo, each for both signs.
+_L2, _L4 = float(np.log(2.0)), float(np.log(4.0))
+SURR_ROWS = [(0.0, 1.5), (0.0, -0.75), (_L2, 1.0), (_L2, -1.0), (_L4, 1.0), (_L4, -1.0),
+             (-_L2, 1.0), (-_L2, -1.0)]
+# SURR_ROWS whose objective has no gradient w.r.t. the ratio (clipped away / dual-clipped)
+SURR_ROWS_ZERO_GRAD = [2, 4, 5, 7]
+
+
+def set_value_rows(value, v_s, ret, idx, first=0):
+    for k, (v, vs, rt) in enumerate(VALUE_ROWS):
+        value[first + k], v_s[idx[first + k]], ret[idx[first + k]] = v, vs, rt
+
+
+def set_surrogate_rows(logp_kernel, logp_old, adv, idx, first):
+    """logp_kernel [B]: the kernel's own log-prob of the minibatch rows (tsrl_gauss_logp /
+    tsrl_cat_logp), so that a log ratio of 0 is exactly 0 in the loss kernel."""
+    for k, (log_ratio, a) in enumerate(SURR_ROWS):
+        j = idx[first + k]
+        logp_old[j] = logp_kernel[first + k] - log_ratio
+        adv[j] = a
+
+
+def check_value_rows(grad_value, B, vf_coef, first=0):
+    """One f32 rounding of the f64 product vf_coef * dv / B lies between dv and the stored
+    gradient: 2^-24 relative; the out-of-range row's gradient is exactly 0."""
+    got = grad_value[first:first + len(VALUE_ROWS)].astype(np.float64) * B / vf_coef
+    np.testing.assert_allclose(got, VALUE_ROWS_DV, rtol=1e-6, atol=0)
+    assert got[-1] == 0.0
+
+
+def _kernel_gauss_logp(mu, log_std, act):
+    from tianshou_amd import _C
+    out = torch.empty(mu.shape[0], dtype=torch.float32, device=mu.device)
+    _C.check(_C.lib().tsrl_gauss_logp(_C.ptr(mu), _C.ptr(log_std), _C.ptr(act), mu.shape[0],
+                                      mu.shape[1], _C.ptr(out), _C.stream_ptr(mu.device)),
+             "tsrl_gauss_logp")
+    return out
+
+
 @pytest.mark.parametrize("kw", CASES)
 @pytest.mark.parametrize("B,A", [(4096, 17), (1000, 6), (257, 1)])
 def test_fused_loss_vs_torch(dev, kw, B, A):
+    _check_fused_loss(dev, kw, B, A)
+
+
+def test_fused_loss_vs_torch_directed(dev):
+    """One more case of test_fused_loss_vs_torch: A = 3 with the directed rows."""
+    assert DIRECTED_N == DIRECTED_B + 37
+    _check_fused_loss(dev, DIRECTED, DIRECTED_B, 3, directed=True)
+
+
+def _check_fused_loss(dev, kw, B, A, directed=False):
     from tianshou_amd import _C
     from tianshou_amd.policy.ppo import _GaussPPOLoss
     from tianshou_amd.dist import DataParallel
@@ -52,6 +116,11 @@ def test_fused_loss_vs_torch(dev, kw, B, A):
     with torch.no_grad():
         lp = Independent(Normal(mu, sp.view(1, -1).exp().expand_as(mu)), 1).log_prob(act[idx])
         logp_old[idx] = lp + torch.randn(B, generator=g) * 0.2
+    d = lambda t: t.to(dev).contiguous()
+    if directed:
+        set_value_rows(value, v_s, ret, idx)
+        lpk = _kernel_gauss_logp(d(mu), d(sp.flatten()), d(act[idx])).cpu()
+        set_surrogate_rows(lpk, logp_old, adv, idx, first=len(VALUE_ROWS))
     eps_clip = kw.get("eps_clip", 0.2)
     want = ref.ppo_gaussian_loss_torch(
         mu, sp.flatten(), value, act[idx], logp_old[idx], adv[idx], ret[idx], v_s[idx],
@@ -61,7 +130,6 @@ def test_fused_loss_vs_torch(dev, kw, B, A):
     p.eps_clip, p.dual_clip = eps_clip, kw.get("dual_clip") or 0.0
     p.vf_coef, p.ent_coef, p.adv_eps, p.b_global = 0.25, kw.get("ent_coef", 0.01), 1e-8, B
     p.value_clip, p.norm_adv = int(kw.get("value_clip", False)), int(kw.get("norm_adv", True))
-    d = lambda t: t.to(dev).contiguous()
     mu_d = d(mu).requires_grad_(True)
     sp_d = d(sp).requires_grad_(True)
     v_d = d(value).requires_grad_(True)
@@ -80,6 +148,10 @@ def test_fused_loss_vs_torch(dev, kw, B, A):
                                atol=1e-6 * float(gw["value"].abs().max()) + 1e-9)
     np.testing.assert_allclose(sp_d.grad.cpu().numpy().flatten(), gw["sigma_param"].numpy(),
                                rtol=1e-4, atol=1e-6 * float(gw["sigma_param"].abs().max()) + 1e-9)
+    if directed:
+        check_value_rows(v_d.grad.cpu().numpy(), B, 0.25)
+        zero = [len(VALUE_ROWS) + k for k in SURR_ROWS_ZERO_GRAD]
+        assert not mu_d.grad[zero].any() and not gw["mu"][zero].any()
 
 
 @pytest.mark.parametrize("tag", ["base", "multi", "clips", "nonorm"])

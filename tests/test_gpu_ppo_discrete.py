@@ -15,6 +15,9 @@ import torch
 
 from oracle import ref
 
+from .test_gpu_ppo import (DIRECTED, DIRECTED_B, DIRECTED_N, VALUE_ROWS, check_value_rows,
+                           set_surrogate_rows, set_value_rows)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -36,11 +39,25 @@ CASES = [
 @pytest.mark.parametrize("kw", CASES)
 @pytest.mark.parametrize("B,A", [(4096, 6), (1000, 2), (257, 18)])
 def test_cat_loss_vs_torch(dev, mode, kw, B, A):
+    _check_cat_loss(dev, mode, kw, B, A, B + 41)
+
+
+# after the saturated rows of mode 1
+_FIRST = 3
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("A", [2, 6])
+def test_cat_loss_vs_torch_directed(dev, mode, A):
+    """One more case of test_cat_loss_vs_torch: the directed rows of test_gpu_ppo.py."""
+    _check_cat_loss(dev, mode, DIRECTED, DIRECTED_B, A, DIRECTED_N, directed=True)
+
+
+def _check_cat_loss(dev, mode, kw, B, A, n, directed=False):
     from tianshou_amd import _C
     from tianshou_amd.dist import DataParallel
-    from tianshou_amd.policy.ppo import _CatPPOLoss
+    from tianshou_amd.policy.ppo import _CatPPOLoss, cat_logp
     g = torch.Generator().manual_seed(B * 3 + A + mode)
-    n = B + 41
     z = torch.randn(B, A, generator=g) * 1.5
     x = z if mode == 0 else torch.softmax(z, -1)
     if mode == 1:  # a few rows with a saturated probability (clamp path of probs_to_logits)
@@ -56,6 +73,11 @@ def test_cat_loss_vs_torch(dev, mode, kw, B, A):
         torch.distributions.Categorical(probs=x)
     with torch.no_grad():
         logp_old[idx] = dist.log_prob(act[idx]) + torch.randn(B, generator=g) * 0.2
+    d = lambda t: t.to(dev).contiguous()  # noqa: E731
+    if directed:
+        set_value_rows(value, v_s, ret, idx, first=_FIRST)
+        lpk = cat_logp(d(x), d(act[idx]), mode).cpu()
+        set_surrogate_rows(lpk, logp_old, adv, idx, first=_FIRST + len(VALUE_ROWS))
     eps_clip = kw.get("eps_clip", 0.2)
     want = ref.ppo_categorical_loss_torch(
         x, value, act[idx], logp_old[idx], adv[idx], ret[idx], v_s[idx], mode,
@@ -65,7 +87,6 @@ def test_cat_loss_vs_torch(dev, mode, kw, B, A):
     p.eps_clip, p.dual_clip = eps_clip, kw.get("dual_clip") or 0.0
     p.vf_coef, p.ent_coef, p.adv_eps, p.b_global = 0.25, kw.get("ent_coef", 0.01), 1e-8, B
     p.value_clip, p.norm_adv = int(kw.get("value_clip", False)), int(kw.get("norm_adv", True))
-    d = lambda t: t.to(dev).contiguous()  # noqa: E731
     x_d = d(x).requires_grad_(True)
     v_d = d(value).requires_grad_(True)
     loss, terms = _CatPPOLoss.apply(x_d, v_d, (d(act), d(logp_old), d(adv), d(ret), d(v_s),
@@ -80,10 +101,57 @@ def test_cat_loss_vs_torch(dev, mode, kw, B, A):
                                atol=1e-6 * float(gw["x"].abs().max()) + 1e-9)
     np.testing.assert_allclose(v_d.grad.cpu().numpy(), gw["value"].numpy(), rtol=1e-4,
                                atol=1e-6 * float(gw["value"].abs().max()) + 1e-9)
-    from tianshou_amd.policy.ppo import cat_logp
     lp = cat_logp(d(x), d(act[idx]), mode).cpu()
     np.testing.assert_allclose(lp.numpy(), dist.log_prob(act[idx]).numpy(), rtol=1e-5,
                                atol=1e-6)
+    if directed:
+        check_value_rows(v_d.grad.cpu().numpy(), B, 0.25, first=_FIRST)
+
+
+def _bits(t):
+    return t.detach().cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("value_clip", [False, True])
+def test_value_loss_same_bits_gauss_and_cat(dev, value_clip):
+    """The Gaussian and the Categorical loss kernel give byte-identical value gradients and
+    value-loss terms on the same value / ret / v_s / idx: both reduce 256-row blocks in the
+    same fixed order, so only the one value_loss definition of csrc/ppo_loss.h lies between
+    these inputs and outputs."""
+    from tianshou_amd import _C
+    from tianshou_amd.dist import DataParallel
+    from tianshou_amd.policy.ppo import _CatPPOLoss, _GaussPPOLoss
+    g = torch.Generator().manual_seed(5)
+    B, n = DIRECTED_B, DIRECTED_N
+    value = torch.randn(B, generator=g)
+    ret = torch.randn(n, generator=g)
+    v_s = ret + torch.randn(n, generator=g) * 0.3
+    adv = torch.randn(n, generator=g) * 2 + 0.3
+    logp_old = torch.randn(n, generator=g) * 0.3 - 3
+    idx = torch.randperm(n, generator=g)[:B]
+    set_value_rows(value, v_s, ret, idx)
+    mu, sp = torch.randn(B, 3, generator=g), torch.randn(3, 1, generator=g) * 0.3 - 0.5
+    act_g = torch.randn(n, 3, generator=g)
+    x = torch.randn(B, 6, generator=g) * 1.5
+    act_c = torch.randint(0, 6, (n,), generator=g)
+    p = _C.PPOParams()
+    p.eps_clip, p.dual_clip = DIRECTED["eps_clip"], DIRECTED["dual_clip"]
+    p.vf_coef, p.ent_coef, p.adv_eps, p.b_global = 0.25, 0.01, 1e-8, B
+    p.value_clip, p.norm_adv = int(value_clip), 0
+    d = lambda t: t.to(dev).contiguous()  # noqa: E731
+    shared = (d(logp_old), d(adv), d(ret), d(v_s), d(idx), p, DataParallel())
+    vg, vc = d(value).requires_grad_(True), d(value).requires_grad_(True)
+    loss_g, terms_g = _GaussPPOLoss.apply(d(mu).requires_grad_(True), d(sp).requires_grad_(True),
+                                          vg, (d(act_g),) + shared)
+    loss_g.backward()
+    loss_c, terms_c = _CatPPOLoss.apply(d(x).requires_grad_(True), vc,
+                                        (d(act_c),) + shared + (0,))
+    loss_c.backward()
+    assert _bits(vg.grad) == _bits(vc.grad)
+    assert _bits(terms_g[2]) == _bits(terms_c[2])
+    assert np.isfinite(vg.grad.cpu().numpy()).all() and vg.grad.abs().max() > 0
+    if value_clip:
+        check_value_rows(vg.grad.cpu().numpy(), B, 0.25)
 
 
 

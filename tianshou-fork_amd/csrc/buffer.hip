@@ -122,16 +122,6 @@ int launch_sum_stage(const float* x, int64_t rows, int64_t cols, int64_t nchunks
 
 using namespace tsrl;
 
-__global__ void ring_advance_kernel(int64_t* rel, int64_t size) { *rel = (*rel + 1) % size; }
-
-extern "C" int tsrl_ring_advance(int64_t* rel_dev, int64_t ring_size, void* stream) {
-    TSRL_CHECK_ARG(rel_dev && ring_size > 0, "tsrl_ring_advance: bad arguments");
-    hipLaunchKernelGGL(ring_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), rel_dev,
-                       ring_size);
-    TSRL_LAUNCH_CHECK("tsrl_ring_advance");
-    return 0;
-}
-
 extern "C" int64_t tsrl_sum_rows_workspace_bytes(int64_t rows, int64_t cols) {
     const int64_t n = sum_rows_nchunks(rows);
     return n > 1 ? n * cols * (int64_t)sizeof(float) : 0;

@@ -23,6 +23,7 @@
 // (B[k=l>>5][j=l&31]) when the A operand is read with the matching permuted k; so layer 2,
 // the heads and the whole backward chain run without moving activations between lanes.
 // Only the weight gradients (which sum over the minibatch rows) transpose through LDS.
+#include "ppo_loss.h"
 #include "x6.h"
 
 namespace tsrl {
@@ -39,7 +40,6 @@ constexpr int H = 64;           // hidden width of each net (fast path)
 constexpr int HC = 2 * H;       // actor + critic first-layer features
 constexpr int NT = HC / 32;     // feature tiles of the concatenated first layer
 constexpr int AMAX = 32;        // action dims padded to one MFMA tile
-constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;
 
 __device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 
@@ -172,13 +172,6 @@ __global__ __launch_bounds__(256, 2) void l1_fwd_kernel(
 // ---------------------------------------------------------------------------------------
 // Tail: layers 2-3 + loss + backward to dZ1 + layer-2/3 weight gradients.
 // ---------------------------------------------------------------------------------------
-struct TailParams {
-    float lo, hi, eps_clip, dual, vf_coef, adv_eps;
-    int value_clip, norm_adv, use_dual, A;
-    float inv_b;
-    double inv_b64;
-};
-
 // per-workgroup slab of weight-gradient partial sums (floats) and loss partial sums (doubles)
 constexpr int SL_W2A = 0, SL_B2A = SL_W2A + H * H, SL_W2C = SL_B2A + H, SL_B2C = SL_W2C + H * H,
               SL_W3A = SL_B2C + H, SL_B3A = SL_W3A + AMAX * H, SL_W3C = SL_B3A + AMAX,
@@ -419,7 +412,7 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
     const float* __restrict__ h1f, int64_t n, const int64_t* __restrict__ idx, TailWeights wt,
     const float* __restrict__ act, const float* __restrict__ logp_old,
     const float* __restrict__ adv, const float* __restrict__ ret, const float* __restrict__ v_s,
-    const double* __restrict__ adv_sums, TailParams p, float* __restrict__ dz1,
+    const double* __restrict__ adv_sums, LossParams p, int A, float* __restrict__ dz1,
     float* __restrict__ slab_f, double* __restrict__ slab_d) {
     constexpr bool actor = NET == 0;
     constexpr int net = NET;
@@ -429,7 +422,6 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
     __shared__ double sred[T16_NW][SL_D];
     const int t = threadIdx.x;
     const int w = t >> 6, l = t & 63, b = l & 15, g = l >> 4;
-    const int A = p.A;
     {
         const float* w2 = actor ? wt.w2a : wt.w2c;
         const float* b2 = actor ? wt.b2a : wt.b2c;
@@ -470,13 +462,7 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
     float* S2 = S1 + H * SH;
     const float b3c = wt.b3c[0];
     float mean_f = 0.0f, std_f = 1.0f;
-    if (actor && p.norm_adv) {
-        const double nn = 1.0 / p.inv_b64;
-        const double m = adv_sums[0] / nn;
-        const double var = (adv_sums[1] - adv_sums[0] * m) / (nn - 1.0);
-        mean_f = (float)m;
-        std_f = (float)sqrt(var > 0.0 ? var : 0.0);
-    }
+    if (actor && p.norm_adv) adv_mean_std(adv_sums, p.inv_b, mean_f, std_f);
     // per-wave accumulators (32x32 C layout of acc_wgrad_x6) and per-lane column sums
     f32x16 gW2[2][2], gW3[1][actor ? 2 : 1];
 #pragma unroll
@@ -586,6 +572,7 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
                 const int a = fc16(g, r >> 2, r & 3);
                 const bool in = a < A && live;
                 const float d = av[r] - (mu[r >> 2][r & 3] + sv[T16_B3 + a]);
+                // not gauss_logp_term: the product with 1 / (2 var) rounds differently
                 const float term = -(d * d) * sv[T16_IV2 + a] - sv[T16_LS + a] - LOG_SQRT_2PI;
                 diff[r] = in ? d : 0.0f;
                 lp += in ? term : 0.0f;
@@ -597,37 +584,10 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
                 float an = x1;
                 if (p.norm_adv) an = (an - mean_f) / (std_f + p.adv_eps);
                 const float ratio = expf(logp - x0);
-                const float surr1 = ratio * an;
-                const float rc = fminf(fmaxf(ratio, p.lo), p.hi);
-                const float surr2 = rc * an;
-                const float in_rng = (ratio >= p.lo && ratio <= p.hi) ? 1.0f : 0.0f;
-                float clip1, d1;
-                if (surr1 < surr2) {
-                    clip1 = surr1;
-                    d1 = an;
-                } else if (surr2 < surr1) {
-                    clip1 = surr2;
-                    d1 = in_rng * an;
-                } else {
-                    clip1 = surr1;
-                    d1 = 0.5f * an + 0.5f * in_rng * an;
-                }
-                float obj = clip1, dobj = d1;
-                if (p.use_dual && an < 0.0f) {
-                    const float tt2 = p.dual * an;
-                    if (clip1 > tt2) {
-                        obj = clip1;
-                    } else if (clip1 < tt2) {
-                        obj = tt2;
-                        dobj = 0.0f;
-                    } else {
-                        obj = clip1;
-                        dobj = 0.5f * d1;
-                    }
-                }
-                g_logp = (float)(-(double)dobj * (double)ratio * p.inv_b64);
+                const Surrogate sg = surrogate(ratio, an, p);
+                g_logp = (float)(-(double)sg.dobj * (double)ratio * p.inv_b);
                 if (g == 0) {
-                    loss_acc += -(double)obj;
+                    loss_acc += -(double)sg.obj;
                     cnt_acc += 1.0;
                 }
             }
@@ -676,34 +636,9 @@ __global__ __launch_bounds__(T16_TPB, 1) void ppo_tail16_kernel(
             const float value = v2 + __shfl_xor(v2, 32, 64) + b3c;
             float gv = 0.0f;
             if (live) {
-                const float rt = x0;
-                float dv, vf;
-                if (p.value_clip) {
-                    const float vs = x1;
-                    const float dlt = value - vs;
-                    const float dcl = fminf(fmaxf(dlt, -p.eps_clip), p.eps_clip);
-                    const float vcl = vs + dcl;
-                    const float e1 = rt - value, e2 = rt - vcl;
-                    const float vf1 = e1 * e1, vf2 = e2 * e2;
-                    const float g1 = -2.0f * e1;
-                    const float g2 = (dlt >= -p.eps_clip && dlt <= p.eps_clip) ? -2.0f * e2 : 0.0f;
-                    if (vf1 > vf2) {
-                        vf = vf1;
-                        dv = g1;
-                    } else if (vf2 > vf1) {
-                        vf = vf2;
-                        dv = g2;
-                    } else {
-                        vf = vf1;
-                        dv = 0.5f * g1 + 0.5f * g2;
-                    }
-                } else {
-                    const float e1 = rt - value;
-                    vf = e1 * e1;
-                    dv = -2.0f * e1;
-                }
-                gv = (float)((double)p.vf_coef * (double)dv * p.inv_b64);
-                if (g == 0) loss_acc += (double)vf;
+                const ValueLoss vl = value_loss(value, x0, x1, p);  // x0 = ret, x1 = v_s
+                gv = (float)((double)p.vf_coef * (double)vl.dv * p.inv_b);
+                if (g == 0) loss_acc += (double)vl.vf;
             }
 #pragma unroll
             for (int ot = 0; ot < 4; ++ot)
@@ -957,7 +892,7 @@ __global__ __launch_bounds__(256, 2) void eval_tail_kernel(const float* __restri
                 const int a = rho(r) + 4 * h;
                 if (a < A && live) {
                     const float diff = av[r] - (mu[r] + sm[E_B3 + a]);
-                    lp += -(diff * diff) / (2.0f * sm[E_VAR + a]) - sm[E_LS + a] - LOG_SQRT_2PI;
+                    lp += gauss_logp_term(diff, sm[E_VAR + a], sm[E_LS + a]);
                 }
             }
             const float logp = lp + __shfl_xor(lp, 32, 64);
@@ -1020,9 +955,9 @@ __device__ __forceinline__ T slab_sum(const T* __restrict__ base, int64_t stride
     return ((sh[o] + sh[64 + o]) + sh[128 + o]) + sh[192 + o];
 }
 
-// Optional loss finalisation folded into the loss-sum block (tsrl_ppo_tail_fin): the work of
-// ppo.hip's gauss_finalize_kernel (loss terms, the log-std gradient) on the sums this block
-// just reduced, so the single-process minibatch needs no separate launch for it.
+// Optional loss finalisation folded into the loss-sum block: the work of ppo.hip's
+// gauss_finalize_kernel (loss terms, the log-std gradient) on the sums this block just
+// reduced, so the single-process minibatch needs no separate launch for it.
 struct TailFin {
     const float* log_std;
     float* losses;        // NULL: no finalisation
@@ -1058,21 +993,8 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(const float* __restric
             __shared__ double fs[64];
             if (threadIdx.x < 64) fs[k0] = s;
             __syncthreads();
-            if (threadIdx.x == 0) {
-                float ent = 0.0f;
-                for (int a = 0; a < A; ++a) {
-                    const float sig = expf(fin.log_std[a]);
-                    ent += 1.4189385332046727f + logf(sig);  // f32(0.5 + 0.5 log 2 pi) + log(scale)
-                }
-                const float clip = (float)(fs[0] * fin.inv_b);
-                const float vf = (float)(fs[1] * fin.inv_b);
-                fin.losses[0] = clip + fin.vf_coef * vf - fin.ent_coef * ent;
-                fin.losses[1] = clip;
-                fin.losses[2] = vf;
-                fin.losses[3] = ent;
-            }
-            for (int a = threadIdx.x; a < A; a += blockDim.x)
-                fin.grad_log_std[a] = (float)(fs[4 + a] - (double)fin.ent_coef);
+            gauss_finalize(fs, A, fin.log_std, fin.vf_coef, fin.ent_coef, fin.inv_b, fin.losses,
+                           fin.grad_log_std);
         }
     }
 }
@@ -1262,23 +1184,6 @@ __global__ __launch_bounds__(256) void dw_reduce_kernel(const float* __restrict_
     }
 }
 
-TailParams make_tail_params(const tsrl_ppo_params& q, int A) {
-    TailParams p;
-    p.lo = (float)(1.0 - q.eps_clip);
-    p.hi = (float)(1.0 + q.eps_clip);
-    p.eps_clip = (float)q.eps_clip;
-    p.dual = (float)q.dual_clip;
-    p.use_dual = q.dual_clip > 0.0;
-    p.vf_coef = (float)q.vf_coef;
-    p.adv_eps = (float)q.adv_eps;
-    p.value_clip = q.value_clip;
-    p.norm_adv = q.norm_adv;
-    p.A = A;
-    p.inv_b = (float)(1.0 / q.b_global);
-    p.inv_b64 = 1.0 / q.b_global;
-    return p;
-}
-
 int tail_grid(int64_t n) {
     // workgroups per net (one launch per net), one resident per CU
     const int64_t tiles = (n + 15) / 16;
@@ -1327,81 +1232,6 @@ extern "C" int64_t tsrl_ppo_tail_workspace_bytes(int64_t n) {
     return (int64_t)g * (SL_F * (int64_t)sizeof(float) + SL_D * (int64_t)sizeof(double)) + 256;
 }
 
-static int ppo_tail_impl(const float* h1frag, int64_t n, const int64_t* idx,
-                         const tsrl_tail_weights* wt, int64_t act_dim, const float* act,
-                         const float* logp_old, const float* adv, const float* ret,
-                         const float* v_s, const double* adv_sums, tsrl_ppo_params prm,
-                         float* dz1, const tsrl_tail_grads* grads, double* sums,
-                         void* workspace, int64_t ws_bytes, TailFin fin, int stages,
-                         void* stream) {
-    TSRL_CHECK_ARG((stages >= 1 && stages <= 3) || stages == 4 || stages == 8,
-                   "tsrl_ppo_tail: stages must be 1, 2, 3, 4 or 8");
-    TSRL_CHECK_ARG(n > 0 && act_dim > 0 && act_dim <= AMAX,
-                   "tsrl_ppo_tail: need n > 0 and 0 < act_dim <= %d", AMAX);
-    TSRL_CHECK_ARG(h1frag && wt && grads && act && logp_old && adv && ret && dz1 && sums &&
-                       workspace,
-                   "tsrl_ppo_tail: null pointer");
-    TSRL_CHECK_ARG(!prm.value_clip || v_s, "tsrl_ppo_tail: value_clip needs v_s");
-    TSRL_CHECK_ARG(!prm.norm_adv || adv_sums, "tsrl_ppo_tail: norm_adv needs adv_sums");
-    TSRL_CHECK_ARG(prm.b_global >= 1.0, "tsrl_ppo_tail: b_global < 1");
-    TSRL_CHECK_ARG(ws_bytes >= tsrl_ppo_tail_workspace_bytes(n), "tsrl_ppo_tail: workspace too small");
-    TSRL_CHECK_ARG(aligned16(h1frag) && aligned16(dz1), "tsrl_ppo_tail: h1frag/dz1 not 16-byte aligned");
-    const int g = tail_grid(n);
-    float* slab_f = reinterpret_cast<float*>(workspace);
-    uintptr_t dptr = reinterpret_cast<uintptr_t>(slab_f + (int64_t)g * SL_F);
-    dptr = (dptr + 15) & ~(uintptr_t)15;
-    double* slab_d = reinterpret_cast<double*>(dptr);
-    TailWeights w{wt->w2a, wt->b2a, wt->w2c, wt->b2c, wt->w3a, wt->b3a, wt->w3c, wt->b3c,
-                  wt->log_std};
-    const TailParams tp = make_tail_params(prm, (int)act_dim);
-    // stages: 1 both nets' tails, 4 / 8 the actor's / the critic's alone (they write disjoint
-    // slab entries and dZ1 halves, so two streams may run them side by side), 2 the reduction
-    if (stages & (1 | 4)) {
-        hipLaunchKernelGGL(ppo_tail16_kernel<0>, dim3(g), dim3(T16_TPB), 0, as_stream(stream),
-                           h1frag, n, idx, w, act, logp_old, adv, ret, v_s, adv_sums, tp, dz1,
-                           slab_f, slab_d);
-        TSRL_LAUNCH_CHECK("tsrl_ppo_tail(actor)");
-    }
-    if (stages & (1 | 8)) {
-        hipLaunchKernelGGL(ppo_tail16_kernel<1>, dim3(g), dim3(T16_TPB), 0, as_stream(stream),
-                           h1frag, n, idx, w, act, logp_old, adv, ret, v_s, adv_sums, tp, dz1,
-                           slab_f, slab_d);
-        TSRL_LAUNCH_CHECK("tsrl_ppo_tail");
-    }
-    if (!(stages & 2)) return 0;
-    TailGrads gg{grads->w2a, grads->b2a, grads->w2c, grads->b2c, grads->w3a, grads->b3a,
-                 grads->w3c, grads->b3c};
-    hipLaunchKernelGGL(tail_reduce_kernel, dim3((SL_F + 63) / 64 + 1), dim3(256), 0,
-                       as_stream(stream), slab_f, slab_d, g, (int)act_dim, gg, sums, fin);
-    TSRL_LAUNCH_CHECK("tsrl_ppo_tail(reduce)");
-    return 0;
-}
-
-extern "C" int tsrl_ppo_tail(const float* h1frag, int64_t n, const int64_t* idx,
-                             const tsrl_tail_weights* wt, int64_t act_dim, const float* act,
-                             const float* logp_old, const float* adv, const float* ret,
-                             const float* v_s, const double* adv_sums, tsrl_ppo_params prm,
-                             float* dz1, const tsrl_tail_grads* grads, double* sums,
-                             void* workspace, int64_t ws_bytes, void* stream) {
-    const TailFin fin{nullptr, nullptr, nullptr, 0.f, 0.f, 0.0};
-    return ppo_tail_impl(h1frag, n, idx, wt, act_dim, act, logp_old, adv, ret, v_s, adv_sums, prm,
-                         dz1, grads, sums, workspace, ws_bytes, fin, 3, stream);
-}
-
-extern "C" int tsrl_ppo_tail_fin(const float* h1frag, int64_t n, const int64_t* idx,
-                                 const tsrl_tail_weights* wt, int64_t act_dim, const float* act,
-                                 const float* logp_old, const float* adv, const float* ret,
-                                 const float* v_s, const double* adv_sums, tsrl_ppo_params prm,
-                                 float* dz1, const tsrl_tail_grads* grads, double* sums,
-                                 void* workspace, int64_t ws_bytes, const float* log_std,
-                                 float* losses, float* grad_log_std, void* stream) {
-    TSRL_CHECK_ARG(log_std && losses && grad_log_std, "tsrl_ppo_tail_fin: null pointer");
-    const TailFin fin{log_std, losses, grad_log_std, (float)prm.vf_coef, (float)prm.ent_coef,
-                      1.0 / prm.b_global};
-    return ppo_tail_impl(h1frag, n, idx, wt, act_dim, act, logp_old, adv, ret, v_s, adv_sums, prm,
-                         dz1, grads, sums, workspace, ws_bytes, fin, 3, stream);
-}
-
 extern "C" int tsrl_ppo_tail_stage(const float* h1frag, int64_t n, const int64_t* idx,
                                    const tsrl_tail_weights* wt, int64_t act_dim, const float* act,
                                    const float* logp_old, const float* adv, const float* ret,
@@ -1411,10 +1241,51 @@ extern "C" int tsrl_ppo_tail_stage(const float* h1frag, int64_t n, const int64_t
                                    float* losses, float* grad_log_std, int stages, void* stream) {
     TSRL_CHECK_ARG((log_std && losses && grad_log_std) || (!log_std && !losses && !grad_log_std),
                    "tsrl_ppo_tail_stage: log_std/losses/grad_log_std all set or all null");
-    const TailFin fin{log_std, losses, grad_log_std, (float)prm.vf_coef, (float)prm.ent_coef,
-                      1.0 / prm.b_global};
-    return ppo_tail_impl(h1frag, n, idx, wt, act_dim, act, logp_old, adv, ret, v_s, adv_sums, prm,
-                         dz1, grads, sums, workspace, ws_bytes, fin, stages, stream);
+    TSRL_CHECK_ARG((stages >= 1 && stages <= 3) || stages == 4 || stages == 8,
+                   "tsrl_ppo_tail_stage: stages must be 1, 2, 3, 4 or 8");
+    TSRL_CHECK_ARG(n > 0 && act_dim > 0 && act_dim <= AMAX,
+                   "tsrl_ppo_tail_stage: need n > 0 and 0 < act_dim <= %d", AMAX);
+    TSRL_CHECK_ARG(h1frag && wt && grads && act && logp_old && adv && ret && dz1 && sums &&
+                       workspace,
+                   "tsrl_ppo_tail_stage: null pointer");
+    TSRL_CHECK_ARG(!prm.value_clip || v_s, "tsrl_ppo_tail_stage: value_clip needs v_s");
+    TSRL_CHECK_ARG(!prm.norm_adv || adv_sums, "tsrl_ppo_tail_stage: norm_adv needs adv_sums");
+    TSRL_CHECK_ARG(prm.b_global >= 1.0, "tsrl_ppo_tail_stage: b_global < 1");
+    TSRL_CHECK_ARG(ws_bytes >= tsrl_ppo_tail_workspace_bytes(n),
+                   "tsrl_ppo_tail_stage: workspace too small");
+    TSRL_CHECK_ARG(aligned16(h1frag) && aligned16(dz1),
+                   "tsrl_ppo_tail_stage: h1frag/dz1 not 16-byte aligned");
+    const int g = tail_grid(n);
+    float* slab_f = reinterpret_cast<float*>(workspace);
+    uintptr_t dptr = reinterpret_cast<uintptr_t>(slab_f + (int64_t)g * SL_F);
+    dptr = (dptr + 15) & ~(uintptr_t)15;
+    double* slab_d = reinterpret_cast<double*>(dptr);
+    TailWeights w{wt->w2a, wt->b2a, wt->w2c, wt->b2c, wt->w3a, wt->b3a, wt->w3c, wt->b3c,
+                  wt->log_std};
+    const LossParams lp = make_loss_params(prm);
+    const int A = (int)act_dim;
+    // stages: 1 both nets' tails, 4 / 8 the actor's / the critic's alone (they write disjoint
+    // slab entries and dZ1 halves, so two streams may run them side by side), 2 the reduction
+    if (stages & (1 | 4)) {
+        hipLaunchKernelGGL(ppo_tail16_kernel<0>, dim3(g), dim3(T16_TPB), 0, as_stream(stream),
+                           h1frag, n, idx, w, act, logp_old, adv, ret, v_s, adv_sums, lp, A, dz1,
+                           slab_f, slab_d);
+        TSRL_LAUNCH_CHECK("tsrl_ppo_tail_stage(actor)");
+    }
+    if (stages & (1 | 8)) {
+        hipLaunchKernelGGL(ppo_tail16_kernel<1>, dim3(g), dim3(T16_TPB), 0, as_stream(stream),
+                           h1frag, n, idx, w, act, logp_old, adv, ret, v_s, adv_sums, lp, A, dz1,
+                           slab_f, slab_d);
+        TSRL_LAUNCH_CHECK("tsrl_ppo_tail_stage(critic)");
+    }
+    if (!(stages & 2)) return 0;
+    TailGrads gg{grads->w2a, grads->b2a, grads->w2c, grads->b2c, grads->w3a, grads->b3a,
+                 grads->w3c, grads->b3c};
+    const TailFin fin{log_std, losses, grad_log_std, lp.vf_coef, lp.ent_coef, lp.inv_b};
+    hipLaunchKernelGGL(tail_reduce_kernel, dim3((SL_F + 63) / 64 + 1), dim3(256), 0,
+                       as_stream(stream), slab_f, slab_d, g, A, gg, sums, fin);
+    TSRL_LAUNCH_CHECK("tsrl_ppo_tail_stage(reduce)");
+    return 0;
 }
 
 extern "C" int64_t tsrl_mlp_dw_workspace_bytes(int64_t n, int64_t D) {

@@ -45,6 +45,7 @@
 // vmcnt(0) drains (hipcc's own LDS-DMA builtin makes every ds_read wait for the next stage):
 // correct, 256-262 us vs 250-256 us for this kernel on the same box -- neither the staging
 // instructions nor the second barrier are what bounds it.
+#include "ppo_loss.h"  // LOG_SQRT_2PI, gauss_logp_term
 #include "x6.h"
 
 namespace tsrl {
@@ -326,7 +327,6 @@ constexpr int RWSTAGE = NPL * HC * ROWB;  // 24 KB
 // (L1 / L2-resident), the layer-1 bias is read from global memory.  Same products in the same
 // order as l1_ring_kernel + eval_tail_kernel: bit-identical values and log-probs.
 constexpr int EH = 64, EAMAX = 32;
-constexpr float E_LOG_SQRT_2PI = 0.91893853320467274178f;
 constexpr int EV_W2 = NPL * 2 * EH * 64;         // one layer-2 image (2 chunks of 32 k)
 constexpr int EV_W3 = NPL * 2 * EAMAX * 64;      // the mu-head image
 // constants (floats): b2a, b2c, b3a (padded), w3c, sigma^2, log sigma
@@ -520,7 +520,7 @@ __device__ __forceinline__ void ev_net(int net, const float (&h1a)[16], const fl
             const int a = rho(r) + 4 * h;
             if (a < A && live) {
                 const float diff = av[r] - (mu[r] + b3[r]);
-                lp += -(diff * diff) / (2.0f * vr[r]) - ls[r] - E_LOG_SQRT_2PI;
+                lp += gauss_logp_term(diff, vr[r], ls[r]);
             }
         }
         const float logp = lp + __shfl_xor(lp, 32, 64);

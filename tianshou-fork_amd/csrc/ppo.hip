@@ -10,7 +10,7 @@
 // terms and of d/d(log_std) are reduced deterministically (fixed order) afterwards.
 // torch's tie rules are reproduced: min/max split the gradient in half on ties, clamp passes
 // it on the closed interval.
-#include "tsrl_common.h"
+#include "ppo_loss.h"
 
 namespace tsrl {
 namespace {
@@ -18,40 +18,11 @@ namespace {
 constexpr int TPB = 256;
 constexpr int NW = TPB / kWave;
 constexpr int MAX_ACT = 64;
-constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;  // math.log(math.sqrt(2*pi))
 
-struct Params {
-    float lo, hi, eps_clip, dual, vf_coef, ent_coef, adv_eps;
-    int value_clip, norm_adv, use_dual;
-    double inv_b;
-};
-
-Params make_params(const tsrl_ppo_params& p) {
-    Params q;
-    q.lo = (float)(1.0 - p.eps_clip);
-    q.hi = (float)(1.0 + p.eps_clip);
-    q.eps_clip = (float)p.eps_clip;
-    q.dual = (float)p.dual_clip;
-    q.use_dual = p.dual_clip > 0.0;
-    q.vf_coef = (float)p.vf_coef;
-    q.ent_coef = (float)p.ent_coef;
-    q.adv_eps = (float)p.adv_eps;
-    q.value_clip = p.value_clip;
-    q.norm_adv = p.norm_adv;
-    q.inv_b = 1.0 / p.b_global;
-    return q;
-}
-
-__global__ __launch_bounds__(TPB) void adv_moments_kernel(const float* adv, const int64_t* idx,
-                                                          int64_t b, double* partials) {
+// Block sums of a per-thread (s, ss) pair: wave sums, then threads 0 and 1 add the waves in
+// order and write out[0] = sum of s, out[1] = sum of ss.
+__device__ __forceinline__ void block_sum2(double s, double ss, double* out) {
     __shared__ double sh[NW][2];
-    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    double s = 0.0, ss = 0.0;
-    if (r < b) {
-        const double a = (double)adv[idx ? idx[r] : r];
-        s = a;
-        ss = a * a;
-    }
     s = wave_sum(s);
     ss = wave_sum(ss);
     const int w = threadIdx.x / kWave;
@@ -63,8 +34,20 @@ __global__ __launch_bounds__(TPB) void adv_moments_kernel(const float* adv, cons
     if (threadIdx.x < 2) {
         double t = 0.0;
         for (int i = 0; i < NW; ++i) t += sh[i][threadIdx.x];
-        partials[2 * blockIdx.x + threadIdx.x] = t;
+        out[threadIdx.x] = t;
     }
+}
+
+__global__ __launch_bounds__(TPB) void adv_moments_kernel(const float* adv, const int64_t* idx,
+                                                          int64_t b, double* partials) {
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    double s = 0.0, ss = 0.0;
+    if (r < b) {
+        const double a = (double)adv[idx ? idx[r] : r];
+        s = a;
+        ss = a * a;
+    }
+    block_sum2(s, ss, partials + 2 * blockIdx.x);
 }
 
 __global__ __launch_bounds__(TPB) void reduce_partials_kernel(const double* partials,
@@ -92,7 +75,6 @@ __global__ __launch_bounds__(TPB) void reduce_partials_kernel(const double* part
 __global__ __launch_bounds__(TPB) void adv_moments_seg_kernel(const float* adv, const int64_t* idx,
                                                               const int64_t* bounds, int nparts,
                                                               double* partials) {
-    __shared__ double sh[NW][2];
     const int g = blockIdx.y;
     const int64_t s0 = bounds[g], s1 = bounds[g + 1];
     double s = 0.0, ss = 0.0;
@@ -102,19 +84,7 @@ __global__ __launch_bounds__(TPB) void adv_moments_seg_kernel(const float* adv, 
         s += a;
         ss += a * a;
     }
-    s = wave_sum(s);
-    ss = wave_sum(ss);
-    const int w = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        sh[w][0] = s;
-        sh[w][1] = ss;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double t = 0.0;
-        for (int i = 0; i < NW; ++i) t += sh[i][threadIdx.x];
-        partials[((int64_t)g * nparts + blockIdx.x) * 2 + threadIdx.x] = t;
-    }
+    block_sum2(s, ss, partials + ((int64_t)g * nparts + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(kWave) void adv_moments_seg_reduce_kernel(const double* partials,
@@ -140,7 +110,7 @@ __global__ __launch_bounds__(kWave) void adv_moments_seg_reduce_kernel(const dou
 __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
     const float* mu, const float* log_std, const float* value, const float* act,
     const float* logp_old, const float* adv, const float* ret, const float* v_s,
-    const int64_t* idx, int64_t b, int64_t A, const double* adv_sums, Params p,
+    const int64_t* idx, int64_t b, int64_t A, const double* adv_sums, LossParams p,
     float* grad_mu, float* grad_value, double* partials) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_mu = smem;             // [TPB * A]
@@ -167,13 +137,7 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
     }
     __syncthreads();
     float mean_f = 0.0f, std_f = 1.0f;
-    if (p.norm_adv) {
-        const double n = 1.0 / p.inv_b;
-        const double m = adv_sums[0] / n;
-        const double var = (adv_sums[1] - adv_sums[0] * m) / (n - 1.0);
-        mean_f = (float)m;
-        std_f = (float)sqrt(var > 0.0 ? var : 0.0);
-    }
+    if (p.norm_adv) adv_mean_std(adv_sums, p.inv_b, mean_f, std_f);
     const int t = threadIdx.x;
     const bool live = t < nrows;
     const int64_t r = r0 + t;
@@ -188,68 +152,16 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
         float logp = 0.0f;
         for (int64_t a = 0; a < A; ++a) {
             const float diff = my_act[a] - my_mu[a];
-            logp += -(diff * diff) / (2.0f * s_var[a]) - s_ls[a] - LOG_SQRT_2PI;
+            logp += gauss_logp_term(diff, s_var[a], s_ls[a]);
         }
         const float ratio = expf(logp - logp_old[j]);
-        const float surr1 = ratio * an;
-        const float rc = fminf(fmaxf(ratio, p.lo), p.hi);
-        const float surr2 = rc * an;
-        const float in_rng = (ratio >= p.lo && ratio <= p.hi) ? 1.0f : 0.0f;
-        float clip1, d1;
-        if (surr1 < surr2) {
-            clip1 = surr1;
-            d1 = an;
-        } else if (surr2 < surr1) {
-            clip1 = surr2;
-            d1 = in_rng * an;
-        } else {
-            clip1 = surr1;
-            d1 = 0.5f * an + 0.5f * in_rng * an;
-        }
-        float obj = clip1, dobj = d1;
-        if (p.use_dual && an < 0.0f) {
-            const float tt = p.dual * an;
-            if (clip1 > tt) {
-                obj = clip1;
-            } else if (clip1 < tt) {
-                obj = tt;
-                dobj = 0.0f;
-            } else {
-                obj = clip1;
-                dobj = 0.5f * d1;
-            }
-        }
-        clip_term = -(double)obj;
-        g_logp = (float)(-(double)dobj * (double)ratio * p.inv_b);
+        const Surrogate sg = surrogate(ratio, an, p);
+        clip_term = -(double)sg.obj;
+        g_logp = (float)(-(double)sg.dobj * (double)ratio * p.inv_b);
 
-        const float v = value[r];
-        const float rt = ret[j];
-        float dv;
-        if (p.value_clip) {
-            const float vs = v_s[j];
-            const float dlt = v - vs;
-            const float dcl = fminf(fmaxf(dlt, -p.eps_clip), p.eps_clip);
-            const float vcl = vs + dcl;
-            const float e1 = rt - v, e2 = rt - vcl;
-            const float vf1 = e1 * e1, vf2 = e2 * e2;
-            const float g1 = -2.0f * e1;
-            const float g2 = (dlt >= -p.eps_clip && dlt <= p.eps_clip) ? -2.0f * e2 : 0.0f;
-            if (vf1 > vf2) {
-                vf_term = vf1;
-                dv = g1;
-            } else if (vf2 > vf1) {
-                vf_term = vf2;
-                dv = g2;
-            } else {
-                vf_term = vf1;
-                dv = 0.5f * g1 + 0.5f * g2;
-            }
-        } else {
-            const float e1 = rt - v;
-            vf_term = (double)(e1 * e1);
-            dv = -2.0f * e1;
-        }
-        grad_value[r] = (float)((double)p.vf_coef * (double)dv * p.inv_b);
+        const ValueLoss vl = value_loss(value[r], ret[j], p.value_clip ? v_s[j] : 0.0f, p);
+        vf_term = (double)vl.vf;
+        grad_value[r] = (float)((double)p.vf_coef * (double)vl.dv * p.inv_b);
     }
     // d/d(mu) into the LDS tile (own row only), d/d(log_std) partials per dim
     for (int64_t a = 0; a < A; ++a) {
@@ -275,6 +187,7 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
     __syncthreads();
     float* gm_blk = grad_mu + r0 * A;
     for (int f = threadIdx.x; f < nel; f += TPB) gm_blk[f] = s_mu[f];
+    // not block_sum2: 4 + A columns per wave, one thread per column
     for (int c = threadIdx.x; c < 4 + A; c += TPB) {
         double tsum = 0.0;
         for (int i = 0; i < NW; ++i) tsum += red[i][c];
@@ -282,23 +195,9 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
     }
 }
 
-__global__ void gauss_finalize_kernel(const double* sums, int64_t A, const float* log_std,
-                                      Params p, float* losses, float* grad_log_std) {
-    if (threadIdx.x == 0) {
-        float ent = 0.0f;
-        for (int64_t a = 0; a < A; ++a) {
-            const float sig = expf(log_std[a]);
-            ent += 1.4189385332046727f + logf(sig);  // f32(0.5 + 0.5*log(2*pi)) + log(scale)
-        }
-        const float clip = (float)(sums[0] * p.inv_b);
-        const float vf = (float)(sums[1] * p.inv_b);
-        losses[0] = clip + p.vf_coef * vf - p.ent_coef * ent;
-        losses[1] = clip;
-        losses[2] = vf;
-        losses[3] = ent;
-    }
-    for (int64_t a = threadIdx.x; a < A; a += blockDim.x)
-        grad_log_std[a] = (float)(sums[4 + a] - (double)p.ent_coef);
+__global__ void gauss_finalize_kernel(const double* sums, int A, const float* log_std,
+                                      LossParams p, float* losses, float* grad_log_std) {
+    gauss_finalize(sums, A, log_std, p.vf_coef, p.ent_coef, p.inv_b, losses, grad_log_std);
 }
 
 __global__ __launch_bounds__(TPB) void gauss_logp_kernel(const float* mu, const float* log_std,
@@ -316,7 +215,7 @@ __global__ __launch_bounds__(TPB) void gauss_logp_kernel(const float* mu, const 
         float lp = 0.0f;
         for (int64_t a = 0; a < A; ++a) {
             const float diff = act[r * A + a] - mu[r * A + a];
-            lp += -(diff * diff) / (2.0f * s_var[a]) - s_ls[a] - LOG_SQRT_2PI;
+            lp += gauss_logp_term(diff, s_var[a], s_ls[a]);
         }
         out[r] = lp;
     }
@@ -390,7 +289,8 @@ extern "C" int tsrl_ppo_gauss_fwd_bwd(const float* mu, const float* log_std, con
     const size_t lds = 2 * (size_t)TPB * (size_t)act_dim * sizeof(float);
     hipLaunchKernelGGL(gauss_fwd_bwd_kernel, dim3((unsigned)tsrl_ppo_num_partials(b)), dim3(TPB),
                        lds, as_stream(stream), mu, log_std, value, act, logp_old, adv, ret, v_s,
-                       idx, b, act_dim, adv_sums, make_params(p), grad_mu, grad_value, partials);
+                       idx, b, act_dim, adv_sums, make_loss_params(p), grad_mu, grad_value,
+                       partials);
     TSRL_LAUNCH_CHECK("tsrl_ppo_gauss_fwd_bwd");
     return 0;
 }
@@ -402,7 +302,7 @@ extern "C" int tsrl_ppo_gauss_finalize(const double* sums, int64_t act_dim, cons
                        act_dim <= MAX_ACT,
                    "tsrl_ppo_gauss_finalize: bad arguments");
     hipLaunchKernelGGL(gauss_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), sums,
-                       act_dim, log_std, make_params(p), losses, grad_log_std);
+                       (int)act_dim, log_std, make_loss_params(p), losses, grad_log_std);
     TSRL_LAUNCH_CHECK("tsrl_ppo_gauss_finalize");
     return 0;
 }

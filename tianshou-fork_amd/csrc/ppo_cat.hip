@@ -12,7 +12,7 @@
 // split the gradient in half and clamp passes it on the closed interval, as torch does.
 // One workgroup = 256 minibatch rows; the [256, nA] tile of x (contiguous, minibatch order)
 // is staged in LDS, the gathered rows of act/logp_old/adv/returns/v_s come through idx.
-#include "tsrl_common.h"
+#include "ppo_loss.h"
 
 namespace tsrl {
 namespace {
@@ -22,28 +22,6 @@ constexpr int NW = TPB / kWave;
 constexpr int MAX_ACT = 64;
 constexpr float F32_EPS = 1.1920928955078125e-07f;
 constexpr float F32_MIN = -3.4028234663852886e+38f;
-
-struct Params {
-    float lo, hi, eps_clip, dual, vf_coef, ent_coef, adv_eps;
-    int value_clip, norm_adv, use_dual;
-    double inv_b;
-};
-
-Params make_params(const tsrl_ppo_params& p) {
-    Params q;
-    q.lo = (float)(1.0 - p.eps_clip);
-    q.hi = (float)(1.0 + p.eps_clip);
-    q.eps_clip = (float)p.eps_clip;
-    q.dual = (float)p.dual_clip;
-    q.use_dual = p.dual_clip > 0.0;
-    q.vf_coef = (float)p.vf_coef;
-    q.ent_coef = (float)p.ent_coef;
-    q.adv_eps = (float)p.adv_eps;
-    q.value_clip = p.value_clip;
-    q.norm_adv = p.norm_adv;
-    q.inv_b = 1.0 / p.b_global;
-    return q;
-}
 
 // Row quantities of the distribution: normalised logits l[] and probabilities q[] (in place
 // over the LDS row), the sum S (probs mode), returns entropy.  clamp masks in m (probs mode).
@@ -95,7 +73,7 @@ __device__ __forceinline__ Row cat_row(float* x, float* l, int A, int mode, uint
 __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
     const float* xin, const float* value, const int64_t* act, const float* logp_old,
     const float* adv, const float* ret, const float* v_s, const int64_t* idx, int64_t b,
-    int A, int mode, const double* adv_sums, Params p, float* grad_x, float* grad_value,
+    int A, int mode, const double* adv_sums, LossParams p, float* grad_x, float* grad_value,
     double* partials) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_x = smem;             // [TPB * A]  x -> probs -> grad
@@ -110,13 +88,7 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
     for (int f = threadIdx.x; f < nel; f += TPB) s_x[f] = x_blk[f];
     __syncthreads();
     float mean_f = 0.0f, std_f = 1.0f;
-    if (p.norm_adv) {
-        const double n = 1.0 / p.inv_b;
-        const double m = adv_sums[0] / n;
-        const double var = (adv_sums[1] - adv_sums[0] * m) / (n - 1.0);
-        mean_f = (float)m;
-        std_f = (float)sqrt(var > 0.0 ? var : 0.0);
-    }
+    if (p.norm_adv) adv_mean_std(adv_sums, p.inv_b, mean_f, std_f);
     const int t = threadIdx.x;
     const bool live = t < nrows;
     double clip_term = 0.0, vf_term = 0.0, ent_term = 0.0;
@@ -133,37 +105,10 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
         float an = adv[j];
         if (p.norm_adv) an = (an - mean_f) / (std_f + p.adv_eps);
         const float ratio = expf(logp - logp_old[j]);
-        const float surr1 = ratio * an;
-        const float rc = fminf(fmaxf(ratio, p.lo), p.hi);
-        const float surr2 = rc * an;
-        const float in_rng = (ratio >= p.lo && ratio <= p.hi) ? 1.0f : 0.0f;
-        float clip1, d1;
-        if (surr1 < surr2) {
-            clip1 = surr1;
-            d1 = an;
-        } else if (surr2 < surr1) {
-            clip1 = surr2;
-            d1 = in_rng * an;
-        } else {
-            clip1 = surr1;
-            d1 = 0.5f * an + 0.5f * in_rng * an;
-        }
-        float obj = clip1, dobj = d1;
-        if (p.use_dual && an < 0.0f) {
-            const float tt = p.dual * an;
-            if (clip1 > tt) {
-                obj = clip1;
-            } else if (clip1 < tt) {
-                obj = tt;
-                dobj = 0.0f;
-            } else {
-                obj = clip1;
-                dobj = 0.5f * d1;
-            }
-        }
-        clip_term = -(double)obj;
+        const Surrogate sg = surrogate(ratio, an, p);
+        clip_term = -(double)sg.obj;
         ent_term = (double)row.H;
-        const float c_lp = (float)(-(double)dobj * (double)ratio * p.inv_b);
+        const float c_lp = (float)(-(double)sg.dobj * (double)ratio * p.inv_b);
         const float c_h = (float)(-(double)p.ent_coef * p.inv_b);
         // d(loss)/dx in place over the probs row
         if (mode == 0) {
@@ -184,34 +129,9 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
             }
             for (int k = 0; k < A; ++k) q[k] = (l[k] - dot) / row.S;
         }
-        const float v = value[r];
-        const float rt = ret[j];
-        float dv;
-        if (p.value_clip) {
-            const float vs = v_s[j];
-            const float dlt = v - vs;
-            const float dcl = fminf(fmaxf(dlt, -p.eps_clip), p.eps_clip);
-            const float vcl = vs + dcl;
-            const float e1 = rt - v, e2 = rt - vcl;
-            const float vf1 = e1 * e1, vf2 = e2 * e2;
-            const float g1 = -2.0f * e1;
-            const float g2 = (dlt >= -p.eps_clip && dlt <= p.eps_clip) ? -2.0f * e2 : 0.0f;
-            if (vf1 > vf2) {
-                vf_term = vf1;
-                dv = g1;
-            } else if (vf2 > vf1) {
-                vf_term = vf2;
-                dv = g2;
-            } else {
-                vf_term = vf1;
-                dv = 0.5f * g1 + 0.5f * g2;
-            }
-        } else {
-            const float e1 = rt - v;
-            vf_term = (double)(e1 * e1);
-            dv = -2.0f * e1;
-        }
-        grad_value[r] = (float)((double)p.vf_coef * (double)dv * p.inv_b);
+        const ValueLoss vl = value_loss(value[r], ret[j], p.value_clip ? v_s[j] : 0.0f, p);
+        vf_term = (double)vl.vf;
+        grad_value[r] = (float)((double)p.vf_coef * (double)vl.dv * p.inv_b);
     }
     const double cs = wave_sum(clip_term);
     const double vs = wave_sum(vf_term);
@@ -226,6 +146,7 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
     __syncthreads();
     float* g_blk = grad_x + r0 * A;
     for (int f = threadIdx.x; f < nel; f += TPB) g_blk[f] = s_x[f];
+    // as gauss_fwd_bwd_kernel's epilogue (same wave order), with 4 columns
     if (threadIdx.x < 4) {
         double tsum = 0.0;
         for (int i = 0; i < NW; ++i) tsum += red[i][threadIdx.x];
@@ -233,7 +154,8 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
     }
 }
 
-__global__ void cat_finalize_kernel(const double* sums, Params p, float* losses) {
+// not ppo_loss.h's gauss_finalize: the entropy here is a reduced sum (sums[3])
+__global__ void cat_finalize_kernel(const double* sums, LossParams p, float* losses) {
     if (threadIdx.x == 0) {
         const float clip = (float)(sums[0] * p.inv_b);
         const float vf = (float)(sums[1] * p.inv_b);
@@ -308,7 +230,7 @@ extern "C" int tsrl_ppo_cat_fwd_bwd(const float* x, const float* value, const in
     const size_t lds = 2 * (size_t)TPB * (size_t)num_actions * sizeof(float);
     hipLaunchKernelGGL(cat_fwd_bwd_kernel, dim3((unsigned)((b + TPB - 1) / TPB)), dim3(TPB), lds,
                        as_stream(stream), x, value, act, logp_old, adv, ret, v_s, idx, b,
-                       (int)num_actions, mode, adv_sums, make_params(p), grad_x, grad_value,
+                       (int)num_actions, mode, adv_sums, make_loss_params(p), grad_x, grad_value,
                        partials);
     TSRL_LAUNCH_CHECK("tsrl_ppo_cat_fwd_bwd");
     return 0;
@@ -318,7 +240,7 @@ extern "C" int tsrl_ppo_cat_finalize(const double* sums, tsrl_ppo_params p, floa
                                      void* stream) {
     TSRL_CHECK_ARG(sums && losses, "tsrl_ppo_cat_finalize: null pointer");
     hipLaunchKernelGGL(cat_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), sums,
-                       make_params(p), losses);
+                       make_loss_params(p), losses);
     TSRL_LAUNCH_CHECK("tsrl_ppo_cat_finalize");
     return 0;
 }

@@ -118,7 +118,6 @@ _SIGS = {
     "tsrl_rms_sum_partials2": ([_p, _p, _p, _i64, _i64, _i64, _p, _p], ctypes.c_int),
     "tsrl_rms_norm_rows": ([_p, _p, _i64, _i64, _p, _p, _f, _f, _p, _p], ctypes.c_int),
     "tsrl_buffer_add": ([ctypes.POINTER(AddArgs), _p], ctypes.c_int),
-    "tsrl_ring_advance": ([_p, _i64, _p], ctypes.c_int),
     "tsrl_collect_pack_floats": ([_i64], _i64),
     "tsrl_collect_pack_w1": ([_p, _i64, _p, _p], ctypes.c_int),
     "tsrl_collect_workspace_bytes": ([_i64, _i64], _i64),
@@ -188,12 +187,6 @@ _SIGS = {
     "tsrl_mlp_l1_fwd_x6": ([_p, _i64, _p, _i64, _i64, _p, _p, _p, ctypes.c_int, _p,
                             ctypes.c_int, _p], ctypes.c_int),
     "tsrl_ppo_tail_workspace_bytes": ([_i64], _i64),
-    "tsrl_ppo_tail": ([_p, _i64, _p, ctypes.POINTER(TailWeights), _i64, _p, _p, _p, _p, _p, _p,
-                       PPOParams, _p, ctypes.POINTER(TailGrads), _p, _p, _i64, _p],
-                      ctypes.c_int),
-    "tsrl_ppo_tail_fin": ([_p, _i64, _p, ctypes.POINTER(TailWeights), _i64, _p, _p, _p, _p, _p,
-                           _p, PPOParams, _p, ctypes.POINTER(TailGrads), _p, _p, _i64, _p, _p,
-                           _p, _p], ctypes.c_int),
     "tsrl_ppo_tail_stage": ([_p, _i64, _p, ctypes.POINTER(TailWeights), _i64, _p, _p, _p, _p,
                              _p, _p, PPOParams, _p, ctypes.POINTER(TailGrads), _p, _p, _i64, _p,
                              _p, _p, ctypes.c_int, _p], ctypes.c_int),

@@ -98,10 +98,11 @@ def main():
                                       _C.ptr(rows_out), 0, s))
 
     def tail():
-        _C.check(L.tsrl_ppo_tail(_C.ptr(h1), B, _C.ptr(idx), fm._tail_w, A, _C.ptr(act),
-                                 _C.ptr(logp_old), _C.ptr(adv), _C.ptr(ret), _C.ptr(v_s),
-                                 _C.ptr(adv_sums), p, _C.ptr(dz1), fm._tail_grads,
-                                 _C.ptr(sums), _C.ptr(ws), ws.numel(), s))
+        _C.check(L.tsrl_ppo_tail_stage(_C.ptr(h1), B, _C.ptr(idx), fm._tail_w, A, _C.ptr(act),
+                                       _C.ptr(logp_old), _C.ptr(adv), _C.ptr(ret), _C.ptr(v_s),
+                                       _C.ptr(adv_sums), p, _C.ptr(dz1), fm._tail_grads,
+                                       _C.ptr(sums), _C.ptr(ws), ws.numel(), None, None, None,
+                                       3, s))
 
     def dw():
         _C.check(L.tsrl_mlp_dw(_C.ptr(dz1), _C.ptr(obs), ld, _C.ptr(idx), B, D,
