@@ -6,7 +6,12 @@ The synthetic env ignores actions, so rewards, flags, env ids and episode statis
 bit-identical; observations pass through obs_rms, whose column sums the fused step folds in a
 different (fixed) order, so normalised rows and statistics agree to f32 rounding (rtol 1e-6);
 actions use the same noise stream and differ only by the actor's f32 summation order
-(rtol / atol 1e-5, as the fused-act tests)."""
+(rtol / atol 1e-5, as the fused-act tests).
+
+Both steps share noise.h, tanh_nb and an actor of the same design, so a mistake they have in
+common is invisible here: tests/test_gpu_actor_ref.py anchors the one-launch step's stored
+actions to an f64 actor (oracle/actor_ref.py) and its noise, cell by cell and across graph
+replays, to counter_normal2's definition."""
 import numpy as np
 import pytest
 import torch

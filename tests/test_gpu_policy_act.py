@@ -1,6 +1,11 @@
 """Fused collector policy step (csrc/policy.hip) vs the torch formulation of
 pg.py:133-171 + base.py:183-215 (actor forward, randn * sigma + mu, clip/tanh, scaling).
-Tolerance rtol/atol 1e-5 (f32 GEMM summation order differs from hipBLASLt's)."""
+Tolerance rtol/atol 1e-5 (f32 GEMM summation order differs from hipBLASLt's).
+
+The absolute anchors of this kernel -- an f64 actor at shape edges (D % 4 != 0, ldx > D, n < 32,
+A = 31 / 32, ragged K batches), the noise stream cell by cell against its definition, tanh_nb in
+ulp and map_action bit for bit -- are in tests/test_gpu_actor_ref.py (references:
+oracle/actor_ref.py); the cases here compare with torch f32 on the GPU."""
 import numpy as np
 import pytest
 import torch
