@@ -758,6 +758,36 @@ int tsrl_clip_rmsprop(float* param, float* grad, float* square_avg, int64_t n, f
                       const float* lr_dev, const tsrl_w1_split* split, int scale_grads,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * DQNPolicy (tianshou/policy/modelfree/dqn.py), csrc/dqn.hip.  Q tables are row-major
+ * [b, num_actions] f32, any num_actions >= 1; every call is one launch unless noted.
+ * tsrl_dqn_target_q: _target_q after the two forwards (:85-96).  q_sel = Q_online(s', .),
+ *   q_eval = Q_target(s', .) (the same pointer without a target network).  is_double:
+ *   out[r] = q_eval[r][argmax_a q_sel[r][a]], else out[r] = max_a q_eval[r][a] (q_sel unread,
+ *   may be NULL); the first index wins ties and a NaN beats every number, as torch's max.
+ * tsrl_dqn_td_fwd_bwd: learn() (:172-185).  td_error[r] = returns[r] - q[r][act[r]];
+ *   *loss = mean(td^2 * weight) (weight NULL: 1), or with huber != 0 torch's
+ *   huber_loss(q_a, returns, reduction="mean") at delta 1 (weight unread, as the reference);
+ *   grad_q[b, num_actions] = d(loss)/dq, written in full (zero off the taken action).  An
+ *   action outside [0, num_actions) gives a NaN td_error and loss and an all-zero gradient
+ *   row.  The loss is an f64 sum in a fixed order (lanes, waves, workgroups): bit-identical
+ *   between runs.  partials: tsrl_dqn_num_partials(b) doubles, read and written only when
+ *   that is > 1 (b > 256: a second one-lane launch folds them), else may be NULL.
+ * tsrl_eps_greedy: exploration_noise (:190-203).  Where u_row[r] < eps: act[r] = argmax_a(
+ *   u_act[r][a] + mask[r][a]) in f64, first index on ties (NumPy's argmax); other rows are
+ *   left as they are.  mask: NULL or uint8 [n, num_actions].
+ * ------------------------------------------------------------------------------- */
+int tsrl_dqn_target_q(const float* q_sel, const float* q_eval, int64_t b, int64_t num_actions,
+                      int is_double, float* out, void* stream);
+int64_t tsrl_dqn_num_partials(int64_t b);
+int tsrl_dqn_td_fwd_bwd(const float* q, const int64_t* act, const float* returns,
+                        const float* weight, int64_t b, int64_t num_actions, int huber,
+                        float* grad_q, float* td_error, double* partials, float* loss,
+                        void* stream);
+int tsrl_eps_greedy(int64_t* act, const double* u_row, const double* u_act,
+                    const uint8_t* mask, double eps, int64_t n, int64_t num_actions,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

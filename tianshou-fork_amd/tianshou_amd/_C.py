@@ -209,6 +209,11 @@ _SIGS = {
     "tsrl_gauss_policy_act": ([_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p,
                                ctypes.c_int, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_mlp_dw": ([_p, _p, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p], ctypes.c_int),
+    "tsrl_dqn_target_q": ([_p, _p, _i64, _i64, ctypes.c_int, _p, _p], ctypes.c_int),
+    "tsrl_dqn_num_partials": ([_i64], _i64),
+    "tsrl_dqn_td_fwd_bwd": ([_p, _p, _p, _p, _i64, _i64, ctypes.c_int, _p, _p, _p, _p, _p],
+                            ctypes.c_int),
+    "tsrl_eps_greedy": ([_p, _p, _p, _p, _d, _i64, _i64, _p], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

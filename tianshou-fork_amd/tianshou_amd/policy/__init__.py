@@ -4,5 +4,7 @@ from tianshou_amd.policy.a2c import A2CPolicy
 from tianshou_amd.policy.ppo import PPOPolicy
 from tianshou_amd.policy.npg import NPGPolicy
 from tianshou_amd.policy.trpo import TRPOPolicy
+from tianshou_amd.policy.dqn import DQNPolicy
 
-__all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy"]
+__all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
+           "DQNPolicy"]

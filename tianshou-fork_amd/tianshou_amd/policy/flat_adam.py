@@ -256,6 +256,12 @@ class FlatAdam:
         self.bind_grads()
         return True
 
+    @property
+    def flat_param(self) -> Optional[torch.Tensor]:
+        """The flat parameter buffer of bind_adam (None while unbound): DQNPolicy lays its
+        target network out the same way, so a hard sync is one copy."""
+        return None if self._adam is None else self._adam["p"]
+
     def flat_offset(self, t: torch.Tensor) -> int:
         """Element offset of parameter storage ``t`` inside the flat parameter buffer."""
         return (t.data_ptr() - self._adam["p"].data_ptr()) // 4

@@ -1414,18 +1414,169 @@ def gen_cartpole():
     _save("cartpole.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 12. DQNPolicy (tianshou/policy/modelfree/dqn.py:11-203): (a) exploration_noise on seeded
+#     NumPy streams, (b) six update() calls of five variants (double / Nature + Huber / no
+#     target net / prioritized / RMSprop) over a small VectorReplayBuffer with episode ends
+#     and one wrapped sub-buffer, (c) an eps = 1.0 collect of the restated CartPole through
+#     the reference Collector with exploration_noise=True.
+# --------------------------------------------------------------------------------------
+DQN_E, DQN_S, DQN_D, DQN_A = 6, 40, 12, 6
+DQN_VARIANTS = {
+    "double": dict(is_double=True, freq=3, n_step=1, huber=False, bs=64, optim="adam"),
+    "nature_huber": dict(is_double=False, freq=2, n_step=3, huber=True, bs=32, optim="adam"),
+    "notarget": dict(is_double=True, freq=0, n_step=2, huber=False, bs=65, optim="adam"),
+    "per": dict(is_double=True, freq=3, n_step=1, huber=False, bs=64, optim="adam", per=True),
+    "rms": dict(is_double=True, freq=3, n_step=1, huber=False, bs=64, optim="rms"),
+}
+
+
+def _dqn_adds(rng):
+    """The add() stream of the learn variants: 34 steps of all six envs, then 12 more of env
+    2 alone, which wraps its 40-row sub-buffer.  Integer actions, random episode ends."""
+    E, D, A = DQN_E, DQN_D, DQN_A
+    adds = []
+    for t in range(34 + 12):
+        ids = np.arange(E) if t < 34 else np.array([2])
+        k = len(ids)
+        done = rng.random(k) < 0.08
+        term = done & (rng.random(k) < 0.5)
+        adds.append(dict(ids=ids, obs=rng.standard_normal((k, D)).astype(np.float32),
+                         act=rng.integers(0, A, k).astype(np.int64),
+                         rew=rng.standard_normal(k), terminated=term, truncated=done & ~term,
+                         obs_next=rng.standard_normal((k, D)).astype(np.float32)))
+    return adds
+
+
+def gen_dqn():
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import DQNPolicy
+    from tianshou.utils.net.common import Net
+    out = {}
+    # (a) exploration_noise
+    cases = []
+    for ci, (bsz, A) in enumerate(((1, 2), (65, 6), (257, 18))):
+        for eps in (0.3, 1.0):
+            for masked in (False, True):
+                rng = np.random.default_rng(100 + len(cases))
+                policy = DQNPolicy(torch.nn.Linear(1, 1), None)
+                policy.max_action_num = A
+                policy.set_eps(eps)
+                act = rng.integers(0, A, bsz).astype(np.int64)
+                mask = rng.random((bsz, A)) < 0.5
+                mask[np.arange(bsz), rng.integers(0, A, bsz)] = True
+                obs = np.zeros((bsz, 1), np.float32)
+                batch = Batch(obs=Batch(obs=obs, mask=mask) if masked else obs)
+                seed = 500 + len(cases)
+                p = f"noise{len(cases)}_"
+                out[p + "act_in"] = act.copy()
+                np.random.seed(seed)
+                out[p + "act_out"] = policy.exploration_noise(act, batch).copy()
+                st = np.random.get_state()
+                out[p + "mask"] = mask
+                out[p + "state_keys"], out[p + "state_pos"] = st[1].copy(), np.array(st[2])
+                cases.append(dict(bsz=bsz, A=A, eps=eps, masked=masked, seed=seed))
+    out["noise_cfg"] = np.array(json.dumps(cases))
+
+    # (b) learn variants
+    E, S, D, A = DQN_E, DQN_S, DQN_D, DQN_A
+    adds = _dqn_adds(np.random.default_rng(41))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    for tag, v in DQN_VARIANTS.items():
+        p = tag + "_"
+        if v.get("per"):
+            buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+        else:
+            buf = VectorReplayBuffer(E * S, E)
+        for a in adds:
+            buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                    buffer_ids=a["ids"])
+        torch.manual_seed(11)
+        net = Net(D, A, hidden_sizes=(16, 16))
+        if v["optim"] == "rms":
+            optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+        else:
+            optim = torch.optim.Adam(net.parameters(), lr=1e-3)
+        policy = DQNPolicy(net, optim, discount_factor=0.97, estimation_step=v["n_step"],
+                           target_update_freq=v["freq"], is_double=v["is_double"],
+                           clip_loss_grad=v["huber"])
+        if tag == "double":  # every variant starts from these weights
+            out.update({"init_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                np.asarray(buf.last_index)
+        process_fn, learn = policy.process_fn, policy.learn
+        seen = []
+
+        def rec_process(batch, buffer, indices):
+            batch = process_fn(batch, buffer, indices)
+            seen.append(dict(indices=np.array(indices, copy=True),
+                             returns=batch.returns.detach().numpy().copy()))
+            if hasattr(batch, "weight"):
+                seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+            return batch
+
+        def rec_learn(batch, **kw):
+            res = learn(batch, **kw)
+            seen[-1]["td_error"] = batch.weight.detach().numpy().copy()
+            return res
+
+        policy.process_fn, policy.learn = rec_process, rec_learn
+        np.random.seed(8)
+        for u in range(6):
+            res = policy.update(v["bs"], buf)
+            q = p + f"u{u}_"
+            out[q + "loss"] = np.array(res["loss"])
+            for k, a in seen[u].items():
+                out[q + k] = a
+            out.update({q + "param_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            if v.get("per"):
+                out[q + "leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+    out["learn_cfg"] = np.array(json.dumps(dict(E=E, S=S, D=D, A=A, gamma=0.97, hidden=[16, 16],
+                                                 seed=8, variants=DQN_VARIANTS)))
+
+    # (c) eps = 1.0 collect
+    sys.path.insert(0, os.path.join(ROOT, "tianshou-fork_amd"))
+    from tianshou_amd.env.cartpole import CartPoleEnv as _CP
+
+    class CartPoleEnv(_CP, gym.Env):  # the reference's venvs accept gymnasium.Env only
+        pass
+
+    seed, n_env, n_step = 1626, 4, 200
+    envs = DummyVectorEnv([lambda: CartPoleEnv() for _ in range(n_env)])
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    envs.seed(seed)
+    net = Net(4, 2, hidden_sizes=(16, 16))
+    policy = DQNPolicy(net, torch.optim.Adam(net.parameters(), lr=1e-3), target_update_freq=10)
+    policy.set_eps(1.0)
+    buf = VectorReplayBuffer(400, n_env)
+    c = Collector(policy, envs, buf, exploration_noise=True)
+    res = c.collect(n_step=n_step)
+    out.update(_stats_arrays("col_", res))
+    out.update(_buf_arrays("col_buf_", buf))
+    out["col_cfg"] = np.array(json.dumps(dict(seed=seed, E=n_env, n_step=n_step, size=400)))
+    _save("dqn.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
-                             "persist", "trainer", "a2c"]
+                             "persist", "trainer", "a2c", "dqn"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
                  rms_wide=gen_rms_wide, rms_fullT=gen_rms_fullT,
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
-                 persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c)
+                 persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn)
     for w in which:
         table[w]()
