@@ -589,9 +589,18 @@ int tsrl_cat_gumbel_argmax(const float* logits, const float* u, int64_t n, int64
  *   [64, D]; Wc, bc: critic [64, D]) -> 128 features per row.  frag_out = 1 writes the MFMA
  *   fragment layout consumed by tsrl_ppo_tail_stage (tsrl_mlp_frag_floats(n) floats); 0 writes
  *   row-major [n, 128].  D and ldx multiples of 4, 16-byte aligned X / W / out.
+ *   Pad rows: with frag_out = 1 both layer-1 entry points (tsrl_mlp_l1_fwd and
+ *   tsrl_mlp_l1_fwd_x6) write ALL tsrl_mlp_frag_floats(n) floats, whatever the buffer held
+ *   before: rows n.. of the last 128-row block hold finite values (tanh(bias) from
+ *   tsrl_mlp_l1_fwd, a copy of row n - 1 from tsrl_mlp_l1_fwd_x6; their content is otherwise
+ *   unspecified).  tests/test_gpu_mlp_bwd.py holds both sides of this.
  * tsrl_ppo_tail_stage: layers 2-3 of both nets, the PPO loss of tsrl_ppo_gauss_fwd_bwd and the
  *   backward to dZ1 [n, 128] (row-major), writing the layer-2/3 parameter gradients of the
  *   mean loss and the loss sums [4 + A] (layout of tsrl_ppo_gauss_finalize's input).
+ *   It REQUIRES those pad rows finite: the rows n.. of the last 16-row tile run through layers
+ *   2-3 like live rows and enter the weight gradients with a zero loss gradient (a product,
+ *   not a select), so a NaN or Inf there would reach every layer-2/3 gradient.  They get
+ *   zero weight: no output depends on their (finite) values.
  * tsrl_mlp_dw: first-layer gradients dW = dZ1^T X[idx], db = column sums of dZ1.  Row
  *   indices idx[] and the pitch ldx must be < 2^32 (the row offsets are 32 x 32-bit
  *   products; ldx is checked).
