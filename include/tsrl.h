@@ -797,6 +797,45 @@ int tsrl_eps_greedy(int64_t* act, const double* u_row, const double* u_act,
                     const uint8_t* mask, double eps, int64_t n, int64_t num_actions,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * C51Policy / QRDQNPolicy (tianshou/policy/modelfree/c51.py, qrdqn.py), csrc/dqn_dist.hip.
+ * Distributions are row-major [b, num_actions, n] f32 (n atoms or quantiles per action);
+ * one workgroup per batch row.
+ * tsrl_dist_select: q[r][a] = sum_k sel[r][a][k] * w[k] (c51.py:71 with w = support), or with
+ *   w NULL the mean over k (qrdqn.py:73); each q is an f64 sum rounded once to f32.
+ *   act[r] = the first index of q[r]'s maximum (a NaN beats every number, the first NaN
+ *   wins, as torch's max); row_out[r][:] = (eval ? eval : sel)[r][act[r]][:], a copy.  q_out
+ *   [b, num_actions], act_out [b] and row_out [b, n] may each be NULL.  One launch; b == 0
+ *   launches nothing.
+ * tsrl_c51_loss_fwd_bwd: learn() and _target_dist's projection (c51.py:82-102).  Per row, with
+ *   z = clamp(returns[r], v_min, v_max): t_i = sum_j clamp(1 - |z_j - support_i| / delta_z, 0,
+ *   1) * next[r][j]; ce[r] = -sum_i t_i log(curr[r][act[r]][i] + 1e-8); *loss = mean(ce *
+ *   weight) (weight NULL: 1); grad[b, num_actions, n] = d(loss)/d(curr), written in full (zero
+ *   off the taken action).  The projected target stays in registers; all arithmetic is f64 on
+ *   the f32 inputs.  2 <= n <= 4096.
+ * tsrl_qr_loss_fwd_bwd: learn() (qrdqn.py:82-93).  With u_ij = returns[r][j] -
+ *   curr[r][act[r]][i], h = smooth_l1(u) at beta 1 and k_ij = |tau_hat[i] - 1{u_ij <= 0}|:
+ *   huber_r = (1/n) sum_ij h_ij k_ij, prio[r] = (1/n) sum_ij h_ij, *loss = mean(huber *
+ *   weight), grad[r][act[r]][i] = -(weight[r] / (b n)) sum_j clamp(u_ij, -1, 1) k_ij (the
+ *   indicator carries no gradient, as in the reference), zero elsewhere.  1 <= n <= 4096.
+ * Both losses: an action outside [0, num_actions) gives a NaN ce / prio and loss and an
+ *   all-zero gradient row.  The loss is an f64 sum in a fixed order (lanes, waves, then the
+ *   rows by a second one-wave launch when b > 1): bit-identical between runs.  partials: b
+ *   doubles, may be NULL when b == 1.
+ * ------------------------------------------------------------------------------- */
+int tsrl_dist_select(const float* sel, const float* eval, const float* w, int64_t b,
+                     int64_t num_actions, int64_t n, float* q_out, int64_t* act_out,
+                     float* row_out, void* stream);
+int tsrl_c51_loss_fwd_bwd(const float* curr, const int64_t* act, const float* next,
+                          const float* returns, const float* support, const float* weight,
+                          int64_t b, int64_t num_actions, int64_t n, float v_min, float v_max,
+                          double delta_z, float* grad, float* ce, double* partials, float* loss,
+                          void* stream);
+int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* returns,
+                         const float* tau_hat, const float* weight, int64_t b,
+                         int64_t num_actions, int64_t n, float* grad, float* prio,
+                         double* partials, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,300 @@
+// The distributional DQN family's small passes: C51Policy (tianshou/policy/modelfree/c51.py) and
+// QRDQNPolicy (qrdqn.py).  The network's output is [b, A, N] (N atoms or quantiles per action).
+//   dist_select:  compute_q_value (c51.py:71, qrdqn.py:73), the greedy action and the gather
+//                 of that action's row (c51.py:74-81, qrdqn.py:59-68) in one launch;
+//   c51_loss:     the categorical projection, the cross-entropy and its gradient
+//                 (c51.py:82-102) without the [b, N, N] projection tensor;
+//   qr_loss:      the pairwise quantile Huber loss, the priorities and the gradient
+//                 (qrdqn.py:82-93) without its [b, N, N] tensors.
+// One workgroup per batch row, lanes over the N atoms (a loop when N exceeds the workgroup):
+// b is 32 to a few hundred, so the grid is b workgroups of one to four waves and the cost is
+// launch latency.  Sums are f64 in a fixed order (lanes by xor butterfly, waves in wave order,
+// rows in row order by the fold launch): bit-identical between runs, no atomics.
+#include "tsrl_common.h"
+
+namespace tsrl {
+namespace {
+
+constexpr int TPB = 256;
+constexpr int NW = TPB / kWave;
+constexpr int64_t kMaxN = 4096;  // the loss kernels stage up to 2 N floats in LDS (32 KiB)
+
+// (v, a) replaces (best, arg) as the row's argmax: torch's rule (the first index of the
+// maximum, the first NaN beats everything), for candidates met in any order.
+__device__ __forceinline__ bool beats_at(float v, int64_t a, float best, int64_t arg) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || a < arg);
+    return v > best || (v == best && a < arg);
+}
+
+// The workgroup's sum of v in wave order, returned to every thread.  red: NW doubles.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    const int t = threadIdx.x;
+    const double ws = wave_sum(v);
+    __syncthreads();  // red may still be read from an earlier call
+    if ((t & (kWave - 1)) == 0) red[t / kWave] = ws;
+    __syncthreads();
+    const int nw = (blockDim.x + kWave - 1) / kWave;
+    double s = 0.0;
+    for (int i = 0; i < nw; ++i) s += red[i];
+    return s;
+}
+
+// Wave w takes actions w, w + NW, ...: lanes over the atoms, an f64 wave sum per action,
+// rounded once to f32.  The waves' candidates meet in LDS; then the whole workgroup copies
+// the chosen action's row.
+__global__ __launch_bounds__(TPB) void dist_select_kernel(
+    const float* __restrict__ sel, const float* __restrict__ eval, const float* __restrict__ w,
+    int64_t A, int64_t N, float* __restrict__ q_out, int64_t* __restrict__ act_out,
+    float* __restrict__ row_out) {
+    __shared__ float s_best[NW];
+    __shared__ int64_t s_arg[NW];
+    __shared__ int64_t s_act;
+    const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+    const int64_t r = blockIdx.x;
+    const float* row = sel + r * A * N;
+    const double inv_n = 1.0 / (double)N;
+    float best = 0.0f;
+    int64_t arg = -1;
+    for (int64_t a = wv; a < A; a += NW) {
+        const float* x = row + a * N;
+        double acc = 0.0;
+        if (w) {
+            for (int64_t n = lane; n < N; n += kWave) acc += (double)x[n] * (double)w[n];
+        } else {
+            for (int64_t n = lane; n < N; n += kWave) acc += (double)x[n];
+        }
+        acc = wave_sum(acc);
+        const float q = (float)(w ? acc : acc * inv_n);
+        if (q_out && lane == 0) q_out[r * A + a] = q;
+        if (arg < 0 || beats_at(q, a, best, arg)) {
+            best = q;
+            arg = a;
+        }
+    }
+    if (lane == 0) {
+        s_best[wv] = best;
+        s_arg[wv] = arg;
+    }
+    __syncthreads();
+    if (t == 0) {
+        best = s_best[0];
+        arg = s_arg[0];  // wave 0 always holds action 0
+        for (int i = 1; i < NW; ++i)
+            if (s_arg[i] >= 0 && beats_at(s_best[i], s_arg[i], best, arg)) {
+                best = s_best[i];
+                arg = s_arg[i];
+            }
+        s_act = arg;
+        if (act_out) act_out[r] = arg;
+    }
+    if (!row_out) return;
+    __syncthreads();
+    const float* src = (eval ? eval : sel) + (r * A + s_act) * N;
+    for (int64_t n = t; n < N; n += TPB) row_out[r * N + n] = src[n];
+}
+
+// A row's loss term: the loss itself when the grid is one row, else that row's partial.
+__device__ __forceinline__ void put_term(double term, double* __restrict__ partials,
+                                         float* __restrict__ loss) {
+    if (gridDim.x == 1)
+        loss[0] = (float)term;
+    else
+        partials[blockIdx.x] = term;
+}
+
+// Zeros over the row's [A, N] gradient tile except the taken action's N entries, which their
+// owners write.
+__device__ __forceinline__ void zero_off_action(float* __restrict__ g_row, int64_t A, int64_t N,
+                                                int64_t a_taken) {
+    const int64_t nel = A * N, lo = a_taken * N, hi = lo + N;
+    for (int64_t f = threadIdx.x; f < nel; f += blockDim.x)
+        if (a_taken < 0 || f < lo || f >= hi) g_row[f] = 0.0f;
+}
+
+// c51.py:82-102 for one row.  LDS: the clamped returns and the next distribution, N floats
+// each.  A thread owns atom i: its projected target t_i is a sum over the N staged pairs and
+// never leaves registers.
+__global__ __launch_bounds__(TPB) void c51_loss_kernel(
+    const float* __restrict__ curr, const int64_t* __restrict__ act,
+    const float* __restrict__ next, const float* __restrict__ returns,
+    const float* __restrict__ support, const float* __restrict__ weight, int64_t b, int64_t A,
+    int64_t N, float v_min, float v_max, double inv_dz, float* __restrict__ grad,
+    float* __restrict__ ce, double* __restrict__ partials, float* __restrict__ loss) {
+    extern __shared__ float lds[];
+    __shared__ double red[NW];
+    float* s_tz = lds;
+    float* s_p = lds + N;
+    const int t = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    const int64_t a64 = act[r];
+    const int64_t a = (a64 >= 0 && a64 < A) ? a64 : -1;
+    float* g_row = grad + r * A * N;
+    zero_off_action(g_row, A, N, a);
+    if (a < 0) {  // invalid action: NaN loss, no gradient
+        if (t == 0) {
+            ce[r] = NAN;
+            put_term((double)NAN, partials, loss);
+        }
+        return;
+    }
+    for (int64_t j = t; j < N; j += blockDim.x) {
+        const float x = returns[r * N + j];
+        s_tz[j] = x != x ? x : fminf(fmaxf(x, v_min), v_max);  // torch's clamp keeps a NaN
+        s_p[j] = next[r * N + j];
+    }
+    __syncthreads();
+    const double wr = weight ? (double)weight[r] : 1.0;
+    const double gscale = wr / (double)b;
+    const float* c_row = curr + (r * A + a) * N;
+    double term = 0.0;
+    for (int64_t i = t; i < N; i += blockDim.x) {
+        const double z = (double)support[i];
+        double ti = 0.0;
+        for (int64_t j = 0; j < N; ++j) {
+            double k = 1.0 - fabs((double)s_tz[j] - z) * inv_dz;
+            k = fmin(fmax(k, 0.0), 1.0);
+            ti += k * (double)s_p[j];
+        }
+        const double c = (double)c_row[i] + 1e-8;
+        term -= ti * log(c);
+        g_row[a * N + i] = (float)(-ti / c * gscale);
+    }
+    const double s = block_sum(term, red);
+    if (t == 0) {
+        ce[r] = (float)s;
+        put_term(s * wr, partials, loss);
+    }
+}
+
+// qrdqn.py:82-93 for one row.  LDS: the target row (returns), N floats.  A thread owns the
+// current quantile i and walks the N targets.
+__global__ __launch_bounds__(TPB) void qr_loss_kernel(
+    const float* __restrict__ curr, const int64_t* __restrict__ act,
+    const float* __restrict__ returns, const float* __restrict__ tau_hat,
+    const float* __restrict__ weight, int64_t b, int64_t A, int64_t N, float* __restrict__ grad,
+    float* __restrict__ prio, double* __restrict__ partials, float* __restrict__ loss) {
+    extern __shared__ float lds[];
+    __shared__ double red[NW];
+    const int t = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    const int64_t a64 = act[r];
+    const int64_t a = (a64 >= 0 && a64 < A) ? a64 : -1;
+    float* g_row = grad + r * A * N;
+    zero_off_action(g_row, A, N, a);
+    if (a < 0) {
+        if (t == 0) {
+            prio[r] = NAN;
+            put_term((double)NAN, partials, loss);
+        }
+        return;
+    }
+    for (int64_t j = t; j < N; j += blockDim.x) lds[j] = returns[r * N + j];
+    __syncthreads();
+    const double wr = weight ? (double)weight[r] : 1.0;
+    const double inv_n = 1.0 / (double)N;
+    const double gscale = wr / ((double)b * (double)N);
+    const float* c_row = curr + (r * A + a) * N;
+    double hub = 0.0, pri = 0.0;
+    for (int64_t i = t; i < N; i += blockDim.x) {
+        const double th = (double)c_row[i], tau = (double)tau_hat[i];
+        const double k_neg = fabs(tau - 1.0), k_pos = fabs(tau);  // |tau - 1{u <= 0}|
+        double hi = 0.0, g = 0.0;
+        for (int64_t j = 0; j < N; ++j) {
+            const double u = (double)lds[j] - th;
+            const double au = fabs(u);
+            const double h = au < 1.0 ? 0.5 * u * u : au - 0.5;  // smooth_l1, beta 1
+            const double k = u <= 0.0 ? k_neg : k_pos;
+            hi += h * k;
+            pri += h;
+            g += fmin(fmax(u, -1.0), 1.0) * k;
+        }
+        hub += hi;
+        g_row[a * N + i] = (float)(-g * gscale);
+    }
+    const double hs = block_sum(hub, red) * inv_n;
+    const double ps = block_sum(pri, red) * inv_n;
+    if (t == 0) {
+        prio[r] = (float)ps;
+        put_term(hs * wr, partials, loss);
+    }
+}
+
+// One wave: lane l sums partials l, l + 64, ... in index order, then the butterfly.
+__global__ __launch_bounds__(kWave) void dist_fold_kernel(const double* __restrict__ partials,
+                                                          int64_t b, float* __restrict__ loss) {
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < b; i += kWave) s += partials[i];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)b);
+}
+
+inline unsigned atom_threads(int64_t N) {
+    const int64_t t = (N + kWave - 1) / kWave * kWave;
+    return (unsigned)(t < TPB ? t : TPB);
+}
+
+}  // namespace
+}  // namespace tsrl
+
+using namespace tsrl;
+
+extern "C" int tsrl_dist_select(const float* sel, const float* eval, const float* w, int64_t b,
+                                int64_t num_actions, int64_t n, float* q_out, int64_t* act_out,
+                                float* row_out, void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 1,
+                   "tsrl_dist_select: need 0 <= b < 2^31, num_actions >= 1 and n >= 1");
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(sel, "tsrl_dist_select: null pointer");
+    hipLaunchKernelGGL(dist_select_kernel, dim3((unsigned)b), dim3(TPB), 0, as_stream(stream),
+                       sel, eval, w, num_actions, n, q_out, act_out, row_out);
+    TSRL_LAUNCH_CHECK("tsrl_dist_select");
+    return 0;
+}
+
+extern "C" int tsrl_c51_loss_fwd_bwd(const float* curr, const int64_t* act, const float* next,
+                                     const float* returns, const float* support,
+                                     const float* weight, int64_t b, int64_t num_actions,
+                                     int64_t n, float v_min, float v_max, double delta_z,
+                                     float* grad, float* ce, double* partials, float* loss,
+                                     void* stream) {
+    TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 2 && n <= kMaxN,
+                   "tsrl_c51_loss_fwd_bwd: need 1 <= b < 2^31, num_actions >= 1, 2 <= n <= %d",
+                   (int)kMaxN);
+    TSRL_CHECK_ARG(v_min < v_max && delta_z > 0.0,
+                   "tsrl_c51_loss_fwd_bwd: need v_min < v_max and delta_z > 0");
+    TSRL_CHECK_ARG(curr && act && next && returns && support && grad && ce && loss && (b == 1 || partials),
+                   "tsrl_c51_loss_fwd_bwd: null pointer");
+    hipLaunchKernelGGL(c51_loss_kernel, dim3((unsigned)b), dim3(atom_threads(n)),
+                       (size_t)(2 * n) * sizeof(float), as_stream(stream), curr, act, next,
+                       returns, support, weight, b, num_actions, n, v_min, v_max,
+                       1.0 / delta_z, grad, ce, partials, loss);
+    TSRL_LAUNCH_CHECK("tsrl_c51_loss_fwd_bwd");
+    if (b > 1) {
+        hipLaunchKernelGGL(dist_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
+                           partials, b, loss);
+        TSRL_LAUNCH_CHECK("tsrl_c51_loss_fwd_bwd (fold)");
+    }
+    return 0;
+}
+
+extern "C" int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* returns,
+                                    const float* tau_hat, const float* weight, int64_t b,
+                                    int64_t num_actions, int64_t n, float* grad, float* prio,
+                                    double* partials, float* loss, void* stream) {
+    TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 1 && n <= kMaxN,
+                   "tsrl_qr_loss_fwd_bwd: need 1 <= b < 2^31, num_actions >= 1, 1 <= n <= %d",
+                   (int)kMaxN);
+    TSRL_CHECK_ARG(curr && act && returns && tau_hat && grad && prio && loss && (b == 1 || partials),
+                   "tsrl_qr_loss_fwd_bwd: null pointer");
+    hipLaunchKernelGGL(qr_loss_kernel, dim3((unsigned)b), dim3(atom_threads(n)),
+                       (size_t)n * sizeof(float), as_stream(stream), curr, act, returns, tau_hat,
+                       weight, b, num_actions, n, grad, prio, partials, loss);
+    TSRL_LAUNCH_CHECK("tsrl_qr_loss_fwd_bwd");
+    if (b > 1) {
+        hipLaunchKernelGGL(dist_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
+                           partials, b, loss);
+        TSRL_LAUNCH_CHECK("tsrl_qr_loss_fwd_bwd (fold)");
+    }
+    return 0;
+}

@@ -214,6 +214,11 @@ _SIGS = {
     "tsrl_dqn_td_fwd_bwd": ([_p, _p, _p, _p, _i64, _i64, ctypes.c_int, _p, _p, _p, _p, _p],
                             ctypes.c_int),
     "tsrl_eps_greedy": ([_p, _p, _p, _p, _d, _i64, _i64, _p], ctypes.c_int),
+    "tsrl_dist_select": ([_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_c51_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _f, _d, _p, _p, _p,
+                               _p, _p], ctypes.c_int),
+    "tsrl_qr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+                             ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

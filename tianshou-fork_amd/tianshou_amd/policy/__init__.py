@@ -5,6 +5,8 @@ from tianshou_amd.policy.ppo import PPOPolicy
 from tianshou_amd.policy.npg import NPGPolicy
 from tianshou_amd.policy.trpo import TRPOPolicy
 from tianshou_amd.policy.dqn import DQNPolicy
+from tianshou_amd.policy.c51 import C51Policy
+from tianshou_amd.policy.qrdqn import QRDQNPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
-           "DQNPolicy"]
+           "DQNPolicy", "C51Policy", "QRDQNPolicy"]

@@ -1,0 +1,92 @@
+"""C51Policy (tianshou/policy/modelfree/c51.py:10-108): categorical DQN, arXiv:1707.06887, on
+DQNPolicy's device path.
+
+The network returns probabilities [b, A, N] over the N atoms of ``support`` (utils/net.py
+``Net(num_atoms=N, softmax=True)``, utils/net_atari.py ``C51``).  Acting and the target
+selection are tsrl_dist_select; learn() is tsrl_c51_loss_fwd_bwd, which projects the target
+distribution (c51.py:82-89) inside the loss kernel instead of building the reference's
+[b, N, N] tensor.  Because the projection needs the greedy atoms at ``batch.obs_next`` under
+the weights of this very update, ``obs_next`` is one more static input of the learn graph: the
+graph holds the no-grad forwards on obs_next, the select launch, the forward on obs, the loss,
+the backward and the flat optimiser pass.  ``fused = False`` runs the reference's op sequence
+on torch.
+"""
+from typing import Any, Optional
+
+import numpy as np
+import torch
+
+from tianshou_amd.data.batch import Batch
+from tianshou_amd.policy.dqn import DQNPolicy
+from tianshou_amd.policy.dqn_dist import DistDQNMixin, _C51Loss
+
+
+class C51Policy(DistDQNMixin, DQNPolicy):
+    """Constructor arguments, defaults, assertions and attributes as the reference's
+    (c51.py:37-63): ``support`` is a non-trainable parameter, ``delta_z`` the atom spacing."""
+
+    def __init__(self, model: torch.nn.Module, optim: torch.optim.Optimizer,
+                 discount_factor: float = 0.99, num_atoms: int = 51, v_min: float = -10.0,
+                 v_max: float = 10.0, estimation_step: int = 1, target_update_freq: int = 0,
+                 reward_normalization: bool = False, **kwargs: Any) -> None:
+        super().__init__(model, optim, discount_factor, estimation_step, target_update_freq,
+                         reward_normalization, **kwargs)
+        assert num_atoms > 1, "num_atoms should be greater than 1"
+        assert v_min < v_max, "v_max should be larger than v_min"
+        self._num_atoms = num_atoms
+        self._v_min = v_min
+        self._v_max = v_max
+        self.support = torch.nn.Parameter(
+            torch.linspace(self._v_min, self._v_max, self._num_atoms), requires_grad=False)
+        self.delta_z = (v_max - v_min) / (num_atoms - 1)
+
+    def _q_weights(self) -> Optional[torch.Tensor]:
+        return self.support
+
+    def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
+        """c51.py:65-66: the support per row; the n-step kernel turns it into
+        r + gamma^n z over N columns."""
+        return self.support.repeat(len(indices), 1)  # [bsz, num_atoms]
+
+    def compute_q_value(self, logits: torch.Tensor, mask) -> torch.Tensor:
+        """c51.py:68-71."""
+        return super().compute_q_value((logits * self.support).sum(2), mask)
+
+    def _target_dist(self, batch: Batch) -> torch.Tensor:
+        """c51.py:73-89 as written: the projected target distribution [b, N] (the fused path
+        never builds it; it is the ``fused = False`` leg and the tests' reference)."""
+        next_dist = self._next_rows(batch)
+        returns = torch.as_tensor(batch.returns, device=next_dist.device)
+        target_support = returns.clamp(self._v_min, self._v_max)
+        target_dist = (1 - (target_support.unsqueeze(1) - self.support.view(1, -1, 1)).abs()
+                       / self.delta_z).clamp(0, 1) * next_dist.unsqueeze(1)
+        return target_dist.sum(-1)
+
+    # -- learn (c51.py:91-108): DQNPolicy.learn with these hooks; batch.weight leaves as the
+    # detached device cross-entropy and the loss is the update's one host read ---------------------
+    def _learn_inputs(self, batch: Batch) -> tuple:
+        return (batch.obs_next,)
+
+    def _before_forward(self, info, obs_next):
+        return self._next_rows(Batch(obs_next=obs_next, info=info))
+
+    def _fused_loss(self, q, act, returns, weight, aux, td_out, loss_out):
+        return _C51Loss.apply(q, (act, aux, returns, self.support.detach(), weight, self._v_min,
+                                  self._v_max, self.delta_z, td_out, loss_out))
+
+    def _learn_torch(self, batch: Batch, weight):
+        """The reference's op sequence as written (c51.py:94-106)."""
+        self.optim.zero_grad()
+        with torch.no_grad():
+            target_dist = self._target_dist(batch)
+        curr_dist = self(batch).logits
+        n = len(curr_dist)
+        act = torch.as_tensor(batch.act, device=curr_dist.device).reshape(n).long()
+        curr_dist = curr_dist[torch.arange(n, device=curr_dist.device), act, :]
+        cross_entropy = -(target_dist * torch.log(curr_dist + 1e-8)).sum(1)
+        w = 1.0 if weight is None else torch.as_tensor(weight, device=curr_dist.device) \
+            .to(curr_dist.dtype)
+        loss = (cross_entropy * w).mean()
+        loss.backward()
+        self.optim.step()
+        return loss.detach(), cross_entropy

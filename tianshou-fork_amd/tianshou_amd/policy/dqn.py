@@ -14,8 +14,12 @@ a captured HIP graph (``graph_learn``).
 
 What stays on torch: observations with an action mask (``obs.mask``), any other optimiser
 (``optim.step()``), and ``fused = False`` -- the reference's op sequence on the GPU, kept as
-the comparison leg of tools/dqn_update_bench.py.  The C51 / QR-DQN / Rainbow subclasses are
-not built.
+the comparison leg of tools/dqn_update_bench.py.
+
+The distributional subclasses C51Policy (policy/c51.py) and QRDQNPolicy (policy/qrdqn.py) fill
+the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_weight``,
+``_before_forward``, ``_fused_loss``) and reuse the flat storage, the sync and the graph replay
+as they are.  RainbowPolicy (NoisyLinear) is not built.
 """
 import warnings
 from copy import deepcopy
@@ -214,10 +218,14 @@ class DQNPolicy(BasePolicy):
         if not hasattr(self, "max_action_num"):
             self.max_action_num = logits.shape[1]
         if mask is None:
-            act = logits.argmax(dim=1)
+            act = self._greedy_act(logits)
         else:
             act = self.compute_q_value(logits, mask).max(dim=1)[1]
         return Batch(logits=logits, act=act, state=hidden)
+
+    def _greedy_act(self, logits: torch.Tensor) -> torch.Tensor:
+        """The unmasked greedy action of forward() (dqn.py:160-162 with mask None)."""
+        return logits.argmax(dim=1)
 
     def exploration_noise(self, act, batch: Batch):
         """dqn.py:190-203.  The two draws come from NumPy's global stream in the reference's
@@ -298,15 +306,17 @@ class DQNPolicy(BasePolicy):
             dev = next(self.model.parameters()).device
             n = len(batch.returns)
             act = torch.as_tensor(batch.act, device=dev).reshape(n).to(torch.int64).contiguous()
-            returns = _f32_rows(batch.returns, dev, n)
-            w = None if weight is None or self._clip_loss_grad else _f32_rows(weight, dev, n)
+            returns = self._returns_rows(batch, dev, n)
+            w = self._loss_weight(weight, dev, n)
+            extra = self._learn_inputs(batch)
             out = None
             if fa is not None:
                 fa.set_lr()
-                if self._warm and net_in is obs and self._graph_ok(net_in, n):
-                    out = self._graph_step(fa, net_in, act, returns, w)
+                if self._warm and net_in is obs and self._graph_ok(net_in, n) and \
+                        all(isinstance(e, torch.Tensor) and e.is_cuda for e in extra):
+                    out = self._graph_step(fa, net_in, act, returns, w, *extra)
             if out is None:
-                out = self._step(fa, net_in, batch.get("info", Batch()), act, returns, w)
+                out = self._step(fa, net_in, batch.get("info", Batch()), act, returns, w, *extra)
             loss, td = out
             self._warm = True
         batch.weight = td.detach()  # prio-buffer
@@ -332,12 +342,33 @@ class DQNPolicy(BasePolicy):
         self.optim.step()
         return loss.detach(), td_error
 
-    def _step(self, fa: Optional[FlatAdam], obs, info, act, returns, weight, td_out=None,
-              loss_out=None):
+    # -- what a subclass's update differs in -----------------------------------------------------
+    def _learn_inputs(self, batch: Batch) -> tuple:
+        """The inputs of one update beyond obs / act / returns / weight (static inputs of the
+        learn graph, handed on to ``_before_forward``)."""
+        return ()
+
+    def _returns_rows(self, batch: Batch, dev, n: int) -> torch.Tensor:
+        return _f32_rows(batch.returns, dev, n)
+
+    def _loss_weight(self, weight, dev, n: int) -> Optional[torch.Tensor]:
+        return None if weight is None or self._clip_loss_grad else _f32_rows(weight, dev, n)
+
+    def _before_forward(self, info, *extra):
+        """No-grad work on the extra inputs ahead of the forward on obs; its result reaches
+        ``_fused_loss``."""
+        return None
+
+    def _fused_loss(self, q, act, returns, weight, aux, td_out, loss_out):
+        """(loss, per-row vector that leaves as batch.weight) of the network output q."""
+        return _DQNLoss.apply(q, (act, returns, weight, self._clip_loss_grad, td_out, loss_out))
+
+    def _step(self, fa: Optional[FlatAdam], obs, info, act, returns, weight, *extra,
+              td_out=None, loss_out=None):
         """Forward, fused TD loss, backward, optimiser step; returns (loss, td_error)."""
+        aux = self._before_forward(info, *extra)
         q, _ = self.model(obs, state=None, info=info)
-        loss, td = _DQNLoss.apply(q, (act, returns, weight, self._clip_loss_grad, td_out,
-                                      loss_out))
+        loss, td = self._fused_loss(q, act, returns, weight, aux, td_out, loss_out)
         if fa is None:
             self.optim.zero_grad()
             loss.backward()
@@ -373,21 +404,22 @@ class DQNPolicy(BasePolicy):
         """The capture context of a learn graph (utils.capture.graph_capture)."""
         return graph_capture(graph)
 
-    def _graph_step(self, fa: FlatAdam, obs, act, returns, weight):
+    def _graph_step(self, fa: FlatAdam, obs, act, returns, weight, *extra):
         """One update's forward, loss, backward and flat optimiser pass replayed from a HIP
         graph captured once per (batch size, observation shape and dtype, flat addresses);
-        static copies of obs / act / returns / weight feed it, the loss and the TD errors come
-        out of static outputs.  None if the capture failed (this and every later update then
-        run eagerly)."""
+        static copies of obs / act / returns / weight (and a subclass's extra inputs) feed it,
+        the loss and the TD errors come out of static outputs.  None if the capture failed
+        (this and every later update then run eagerly)."""
         fa.bind_grads()
         addr = (fa.flat_grad.data_ptr(), tuple(p.data_ptr() for p in fa.params))
         if self._learn_graphs and next(iter(self._learn_graphs.values()))["addr"] != addr:
             self._learn_graphs.clear()
-        key = (len(act), tuple(obs.shape), obs.dtype, weight is not None)
+        key = (len(act), tuple(obs.shape), obs.dtype, weight is not None,
+               tuple((tuple(e.shape), e.dtype) for e in extra))
         st = self._learn_graphs.get(key)
         if st is None:
             static = [obs.clone(), act.clone(), returns.clone(),
-                      None if weight is None else weight.clone()]
+                      None if weight is None else weight.clone(), *(e.clone() for e in extra)]
             td = torch.empty(len(act), dtype=torch.float32, device=act.device)
             loss = torch.empty((), dtype=torch.float32, device=act.device)
             torch.cuda.synchronize()
@@ -404,7 +436,7 @@ class DQNPolicy(BasePolicy):
             st = self._learn_graphs[key] = dict(addr=addr, graph=graph, static=static, td=td,
                                                 loss=loss)
         else:
-            for d, a in zip(st["static"], (obs, act, returns, weight)):
+            for d, a in zip(st["static"], (obs, act, returns, weight, *extra)):
                 if d is not None:
                     d.copy_(a)
         st["graph"].replay()

@@ -464,3 +464,35 @@ class DQN(nn.Module):
         else:
             x = (obs / self.scale).to(torch.float32) if self.scale else obs.to(torch.float32)
         return self.net(x), state
+
+
+class C51(DQN):
+    """atari_network.py:88-118: the DQN trunk with an A * N head, softmax over the N atoms,
+    returned as [b, A, N]."""
+
+    def __init__(self, c: int, h: int, w: int, action_shape: Sequence[int], num_atoms: int = 51,
+                 device="cpu") -> None:
+        self.action_num = int(np.prod(action_shape))
+        super().__init__(c, h, w, [self.action_num * num_atoms], device)
+        self.num_atoms = num_atoms
+
+    def forward(self, obs, state: Any = None, info: Dict[str, Any] = {},
+                rows: Optional[torch.Tensor] = None):
+        obs, state = super().forward(obs, rows=rows)
+        obs = obs.view(-1, self.num_atoms).softmax(dim=-1)
+        return obs.view(-1, self.action_num, self.num_atoms), state
+
+
+class QRDQN(DQN):
+    """atari_network.py:182-212: the DQN trunk with an A * N head, returned as [b, A, N]."""
+
+    def __init__(self, c: int, h: int, w: int, action_shape: Sequence[int],
+                 num_quantiles: int = 200, device="cpu") -> None:
+        self.action_num = int(np.prod(action_shape))
+        super().__init__(c, h, w, [self.action_num * num_quantiles], device)
+        self.num_quantiles = num_quantiles
+
+    def forward(self, obs, state: Any = None, info: Dict[str, Any] = {},
+                rows: Optional[torch.Tensor] = None):
+        obs, state = super().forward(obs, rows=rows)
+        return obs.view(-1, self.action_num, self.num_quantiles), state

@@ -1565,18 +1565,147 @@ def gen_dqn():
     _save("dqn.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 21. C51Policy (tianshou/policy/modelfree/c51.py) and QRDQNPolicy (qrdqn.py): six update()
+#     calls per variant over gen_dqn's add() stream.  Besides what gen_dqn records, every
+#     variant carries the smallest relative gap between the best and the second-best Q-value
+#     (f64, from the recorded run's own f32 network outputs) over every row whose greedy
+#     action the trace uses (the online network at obs_next): the seeds below keep it >= 1e-4,
+#     so an f32 summation-order difference cannot flip a recorded action.
+# --------------------------------------------------------------------------------------
+DIST_C51 = dict(num_atoms=21, v_min=-4.0, v_max=4.0)
+DIST_QR = dict(num_quantiles=17)
+DIST_VARIANTS = {
+    "c51_target": dict(kind="c51", freq=2, n_step=3, bs=32, optim="adam"),
+    "c51_notarget": dict(kind="c51", freq=0, n_step=1, bs=65, optim="adam"),
+    "c51_per": dict(kind="c51", freq=2, n_step=1, bs=64, optim="adam", per=True),
+    "qr_target": dict(kind="qr", freq=3, n_step=1, bs=64, optim="adam"),
+    "qr_notarget": dict(kind="qr", freq=0, n_step=2, bs=65, optim="adam"),
+    "qr_per": dict(kind="qr", freq=3, n_step=1, bs=32, optim="adam", per=True),
+    "qr_rms": dict(kind="qr", freq=3, n_step=1, bs=64, optim="rms"),
+}
+DIST_INIT_SEED = {"c51": 11, "qr": 11}
+DIST_SAMPLE_SEED = 8
+
+
+def _top2_gap(q):
+    """min over rows of (best - second) / max(|best|, |second|), f64."""
+    q = np.sort(np.asarray(q, np.float64), axis=1)
+    if q.shape[1] < 2:
+        return np.inf
+    best, second = q[:, -1], q[:, -2]
+    return float(((best - second) / np.maximum(np.abs(best), np.abs(second))).min())
+
+
+def gen_dist_dqn():
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import C51Policy, QRDQNPolicy
+    from tianshou.utils.net.common import Net
+    out = {}
+    E, S, D, A = DQN_E, DQN_S, DQN_D, DQN_A
+    adds = _dqn_adds(np.random.default_rng(41))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    for tag, v in DIST_VARIANTS.items():
+        p = tag + "_"
+        if v.get("per"):
+            buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+        else:
+            buf = VectorReplayBuffer(E * S, E)
+        for a in adds:
+            buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                    buffer_ids=a["ids"])
+        kind = v["kind"]
+        torch.manual_seed(DIST_INIT_SEED[kind])
+        if kind == "c51":
+            net = Net(D, A, hidden_sizes=(16, 16), softmax=True, num_atoms=DIST_C51["num_atoms"])
+        else:
+            net = Net(D, A, hidden_sizes=(16, 16), num_atoms=DIST_QR["num_quantiles"])
+        if v["optim"] == "rms":
+            optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+        else:
+            optim = torch.optim.Adam(net.parameters(), lr=1e-3)
+        kw = dict(discount_factor=0.97, estimation_step=v["n_step"],
+                  target_update_freq=v["freq"])
+        if kind == "c51":
+            policy = C51Policy(net, optim, **DIST_C51, **kw)
+        else:
+            policy = QRDQNPolicy(net, optim, **DIST_QR, **kw)
+        if not any(k.startswith("init_" + kind + "_") for k in out):  # one start per family
+            out.update({"init_" + kind + "_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                np.asarray(buf.last_index)
+        process_fn, learn, forward = policy.process_fn, policy.learn, policy.forward
+        seen, gaps = [], []
+
+        def rec_forward(batch, state=None, model="model", input="obs", **kw_):
+            res = forward(batch, state, model=model, input=input, **kw_)
+            if model == "model" and input == "obs_next":
+                z64 = res.logits.detach().double()
+                q64 = (z64 * policy.support.double()).sum(2) if kind == "c51" else z64.mean(2)
+                gaps.append(_top2_gap(q64.numpy()))
+            return res
+
+        def rec_process(batch, buffer, indices):
+            batch = process_fn(batch, buffer, indices)
+            seen.append(dict(indices=np.array(indices, copy=True),
+                             returns=batch.returns.detach().numpy().copy()))
+            if hasattr(batch, "weight"):
+                seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+            return batch
+
+        def rec_target_dist(batch):  # the projected target of the update (after its sync)
+            t = target_dist(batch)
+            seen[-1]["target_dist"] = t.detach().numpy().copy()
+            return t
+
+        def rec_learn(batch, **kw_):
+            res = learn(batch, **kw_)
+            seen[-1]["out_weight"] = batch.weight.detach().numpy().copy()
+            return res
+
+        policy.process_fn, policy.learn, policy.forward = rec_process, rec_learn, rec_forward
+        if kind == "c51":
+            target_dist, policy._target_dist = policy._target_dist, rec_target_dist
+        np.random.seed(DIST_SAMPLE_SEED)
+        for u in range(6):
+            res = policy.update(v["bs"], buf)
+            q = p + f"u{u}_"
+            out[q + "loss"] = np.array(res["loss"])
+            for k, a in seen[u].items():
+                out[q + k] = a
+            out.update({q + "param_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            if v.get("per"):
+                out[q + "leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+        assert len(gaps) == 6, (tag, len(gaps))
+        out[p + "top2_gap"] = np.array(min(gaps))
+        print(tag, "top-two gap", min(gaps))
+        assert min(gaps) >= 1e-4, (tag, min(gaps))
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=E, S=S, D=D, A=A, gamma=0.97, hidden=[16, 16], seed=DIST_SAMPLE_SEED, c51=DIST_C51,
+        qr=DIST_QR, variants=DIST_VARIANTS)))
+    _save("dist_dqn.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
-                             "persist", "trainer", "a2c", "dqn"]
+                             "persist", "trainer", "a2c", "dqn", "dist_dqn"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
                  rms_wide=gen_rms_wide, rms_fullT=gen_rms_fullT,
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
-                 persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn)
+                 persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn,
+                 dist_dqn=gen_dist_dqn)
     for w in which:
         table[w]()
