@@ -836,6 +836,43 @@ int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* ret
                          int64_t num_actions, int64_t n, float* grad, float* prio,
                          double* partials, float* loss, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * DDPGPolicy / TD3Policy (tianshou/policy/modelfree/ddpg.py, td3.py), csrc/ddpg.hip.  Every
+ * call is one launch unless noted; all tensors f32 unless noted.
+ * tsrl_soft_update: sync_weight (ddpg.py:117-120, td3.py:93-96) over up to four (target,
+ *   source, n) segments: t = fl(fl(tau_f s) + fl(omt_f t)) with tau_f = (float)tau and omt_f =
+ *   (float)(1.0 - tau), no FMA -- torch's fp32 `tau * s + (1 - tau) * t` bit for bit.  A
+ *   segment with n == 0 is skipped (its pointers may be NULL); segments need 4-byte alignment
+ *   only and must not overlap.  0 <= tau <= 1.
+ * tsrl_td3_smooth: td3.py:100-104 over n = b * act_dim elements: out = fl(act + clamp(fl(noise
+ *   * (float)sigma), -clip, clip)), the clamp skipped when clip <= 0; a NaN passes the clamp
+ *   as through torch.clamp.  out may be act (in place).
+ * tsrl_q_mse_fwd_bwd: _mse_optimizer (ddpg.py:173-178) for one critic (q2 NULL) or two, each
+ *   [b].  td_k = q_k - returns; loss[k] = mean(td_k^2 * weight) (weight NULL: 1); grad_k[r] =
+ *   2 td_k weight / b; td_out[r] = td_1, or with two critics fl(fl(td_1 + td_2) / 2)
+ *   (td3.py:119).  total (may be NULL) receives the sum of the losses.  Each loss is an f64 sum
+ *   in a fixed order (lanes, waves, workgroups): bit-identical between runs.  partials: 2 *
+ *   tsrl_ddpg_num_partials(b) doubles, read and written only when that count is > 1 (b > 256:
+ *   a second one-lane launch folds them), else may be NULL.
+ * tsrl_neg_mean_fwd_bwd: the actor loss (ddpg.py:189): *loss = -mean(q) as the same fixed-order
+ *   f64 sum, grad[r] = -1.0f / (float)b.  partials: tsrl_ddpg_num_partials(b) doubles, as above.
+ * tsrl_act_noise: exploration_noise (ddpg.py:202) over n elements: out = (float)((double)act +
+ *   noise), noise f64 (NumPy's draws).
+ * ------------------------------------------------------------------------------- */
+int tsrl_soft_update(float* t0, const float* s0, int64_t n0, float* t1, const float* s1,
+                     int64_t n1, float* t2, const float* s2, int64_t n2, float* t3,
+                     const float* s3, int64_t n3, double tau, void* stream);
+int tsrl_td3_smooth(const float* act, const float* noise, double sigma, double clip, int64_t n,
+                    float* out, void* stream);
+int64_t tsrl_ddpg_num_partials(int64_t b);
+int tsrl_q_mse_fwd_bwd(const float* q1, const float* q2, const float* returns,
+                       const float* weight, int64_t b, float* grad1, float* grad2,
+                       float* td_out, double* partials, float* loss, float* total,
+                       void* stream);
+int tsrl_neg_mean_fwd_bwd(const float* q, int64_t b, float* grad, double* partials, float* loss,
+                          void* stream);
+int tsrl_act_noise(const float* act, const double* noise, int64_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,13 @@ _SIGS = {
                                _p, _p], ctypes.c_int),
     "tsrl_qr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
                              ctypes.c_int),
+    "tsrl_soft_update": ([_p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _d, _p],
+                         ctypes.c_int),
+    "tsrl_td3_smooth": ([_p, _p, _d, _d, _i64, _p, _p], ctypes.c_int),
+    "tsrl_ddpg_num_partials": ([_i64], _i64),
+    "tsrl_q_mse_fwd_bwd": ([_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_neg_mean_fwd_bwd": ([_p, _i64, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_act_noise": ([_p, _p, _i64, _p, _p], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

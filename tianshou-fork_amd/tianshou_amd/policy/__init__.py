@@ -7,6 +7,8 @@ from tianshou_amd.policy.trpo import TRPOPolicy
 from tianshou_amd.policy.dqn import DQNPolicy
 from tianshou_amd.policy.c51 import C51Policy
 from tianshou_amd.policy.qrdqn import QRDQNPolicy
+from tianshou_amd.policy.ddpg import DDPGPolicy
+from tianshou_amd.policy.td3 import TD3Policy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
-           "DQNPolicy", "C51Policy", "QRDQNPolicy"]
+           "DQNPolicy", "C51Policy", "QRDQNPolicy", "DDPGPolicy", "TD3Policy"]

@@ -215,6 +215,24 @@ class ActorProb(_PreprocessWrapper):
         return (mu, sigma), state
 
 
+class Actor(_PreprocessWrapper):
+    """Deterministic actor (continuous.py:31-84): preprocess -> MLP ``last`` ->
+    max_action * tanh.  DDPGPolicy's and TD3Policy's actor."""
+
+    def __init__(self, preprocess_net, action_shape, hidden_sizes=(), max_action=1.0,
+                 device="cpu", preprocess_net_output_dim=None):
+        super().__init__(preprocess_net, device=device)
+        self.output_dim = int(np.prod(action_shape))
+        input_dim = getattr(preprocess_net, "output_dim", preprocess_net_output_dim)
+        self.last = MLP(input_dim, self.output_dim, hidden_sizes, device=self.device)
+        self.max_action = max_action
+
+    def forward(self, obs, state=None, info: Dict[str, Any] = {}):
+        logits, hidden = self.preprocess(obs, state)
+        logits = self.max_action * torch.tanh(self.last(logits))
+        return logits, hidden
+
+
 class Critic(_PreprocessWrapper):
     """V(s) head (continuous.py:87-150)."""
 

@@ -1,0 +1,118 @@
+"""Time DDPGPolicy.update() and TD3Policy.update() (sample + process_fn + learn +
+post_process_fn) on one filled VectorReplayBuffer: HIP events around each of --updates updates
+after --warmup.
+
+    python tools/ddpg_update_bench.py              # both policies, both shapes, three legs
+
+Shapes: "d17" obs 17 / act 6 (examples/mujoco/mujoco_td3.py on HalfCheetah) and "d376" obs 376 /
+act 17 (Humanoid), hidden (256, 256), batch 256, Adam, n_step 1; TD3 with its default
+update_actor_freq 2, so its mean covers both step kinds.
+Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), "eager"
+(graph_learn=False: the fused kernels and the flat Adam passes launched eagerly) and "torch"
+(fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
+update), the torch leg --torch-runs times to show its spread.
+
+Prints one JSON line per (policy, shape, leg, run)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.append(os.path.join(ROOT, "tianshou-fork_amd"))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--policies", default="ddpg,td3")
+ap.add_argument("--configs", default="d17,d376")
+ap.add_argument("--legs", default="graph,eager,torch")
+ap.add_argument("--updates", type=int, default=50)
+ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--torch-runs", type=int, default=3)
+args = ap.parse_args()
+
+from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
+from tianshou_amd.policy import DDPGPolicy, TD3Policy  # noqa: E402
+from tianshou_amd.utils.net import Actor, Critic, Net  # noqa: E402
+
+dev = torch.device("cuda", 0)
+CONFIGS = {
+    "d17": dict(E=8, T=512, D=17, A=6, batch=256),
+    "d376": dict(E=8, T=512, D=376, A=17, batch=256),
+}
+HIDDEN = (256, 256)
+LEGS = {"graph": dict(graph_learn=True), "eager": dict(graph_learn=False),
+        "torch": dict(fused=False)}
+
+
+def fill(cfg):
+    """Random transitions, episodes ending at 2 % of the steps."""
+    E, T, D, A = cfg["E"], cfg["T"], cfg["D"], cfg["A"]
+    buf = VectorReplayBuffer(E * T, E, device=dev)
+    rng = np.random.default_rng(0)
+    obs = rng.standard_normal((E, D)).astype(np.float32)
+    for _ in range(T):
+        nxt = rng.standard_normal((E, D)).astype(np.float32)
+        done = rng.random(E) < 0.02
+        term = done & (rng.random(E) < 0.5)
+        buf.add(Batch(obs=obs, act=rng.uniform(-1, 1, (E, A)).astype(np.float32),
+                      rew=rng.standard_normal(E), terminated=term, truncated=done & ~term,
+                      obs_next=nxt), buffer_ids=np.arange(E))
+        obs = nxt
+    return buf
+
+
+def make_policy(kind, cfg, leg):
+    torch.manual_seed(0)
+    D, A = cfg["D"], cfg["A"]
+    actor = Actor(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev).to(dev)
+    critics = [Critic(Net(D, A, hidden_sizes=HIDDEN, concat=True, device=dev), device=dev)
+               .to(dev) for _ in range(1 if kind == "ddpg" else 2)]
+    a_opt = torch.optim.Adam(actor.parameters(), lr=3e-4)
+    c_opt = [torch.optim.Adam(c.parameters(), lr=3e-4) for c in critics]
+    kw = dict(tau=0.005, gamma=0.99, exploration_noise=None, estimation_step=1,
+              action_scaling=False)
+    if kind == "ddpg":
+        policy = DDPGPolicy(actor, a_opt, critics[0], c_opt[0], **kw)
+    else:
+        policy = TD3Policy(actor, a_opt, critics[0], c_opt[0], critics[1], c_opt[1], **kw)
+    policy = policy.to(dev)
+    for k, v in LEGS[leg].items():
+        setattr(policy, k, v)
+    return policy
+
+
+for kind in args.policies.split(","):
+    for name in args.configs.split(","):
+        cfg = CONFIGS[name]
+        buf = fill(cfg)
+        for leg in args.legs.split(","):
+            for run in range(args.torch_runs if leg == "torch" else 1):
+                policy = make_policy(kind, cfg, leg)
+                np.random.seed(0)
+                torch.manual_seed(1)
+                ms, last = [], None
+                for u in range(args.warmup + args.updates):
+                    t0 = torch.cuda.Event(enable_timing=True)
+                    t1 = torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    last = policy.update(cfg["batch"], buf)
+                    t1.record()
+                    t1.synchronize()
+                    if u >= args.warmup:
+                        ms.append(t0.elapsed_time(t1))
+                assert all(np.isfinite(v) for v in last.values())
+                ms = np.asarray(ms)
+                print(json.dumps({
+                    "policy": kind, "config": name, "leg": leg, "run": run,
+                    "batch": cfg["batch"], "obs": cfg["D"], "act": cfg["A"],
+                    "updates": args.updates, "update_ms_mean": round(float(ms.mean()), 4),
+                    "update_ms_median": round(float(np.median(ms)), 4),
+                    "update_ms_min": round(float(ms.min()), 4),
+                    "update_ms_max": round(float(ms.max()), 4),
+                    "graphs": len(policy._learn_graphs),
+                    "flat_optimiser": bool(policy._flats) and all(
+                        policy._flat_pair(n) is not None for n in policy._sync_order),
+                    "last": {k: round(float(v), 6) for k, v in last.items()}}), flush=True)

@@ -1693,12 +1693,266 @@ def gen_dist_dqn():
     _save("dist_dqn.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 22. DDPGPolicy (tianshou/policy/modelfree/ddpg.py) and TD3Policy (td3.py):
+#     (a) exploration_noise (ddpg.py:196-204) over the noise processes of
+#         tianshou/exploration/random.py, with NumPy's state afterwards;
+#     (b) six update() calls per variant over one add() stream shaped like _dqn_adds with float
+#         actions; every torch.randn draw (td3.py:101) is recorded, because a device generator
+#         cannot reproduce the CPU stream.  Each recorded quantity is one array per variant,
+#         the six updates stacked; "params" rows are _flat_params' vectors;
+#     (c) one Collector.collect(exploration_noise=True) over the action-coupled synthetic Box
+#         env with a non-symmetric action Box.  The actor's output layer is zeroed, so its
+#         action is exactly 0 whatever GEMM computes it and the stored action is the noise draw
+#         alone: the rounded f64 actions can then be asserted bit for bit.
+# --------------------------------------------------------------------------------------
+DDPG_D, DDPG_A = 5, 3
+DDPG_VARIANTS = {
+    "ddpg": dict(kind="ddpg", n_step=1, bs=64, optim="adam"),
+    "ddpg_nstep": dict(kind="ddpg", n_step=3, bs=65, optim="adam"),
+    "ddpg_per": dict(kind="ddpg", n_step=1, bs=32, optim="adam", per=True),
+    "ddpg_rms": dict(kind="ddpg", n_step=1, bs=64, optim="rms"),
+    "td3": dict(kind="td3", n_step=1, bs=64, optim="adam", freq=2, policy_noise=0.2,
+                noise_clip=0.5),
+    "td3_noclip": dict(kind="td3", n_step=2, bs=65, optim="adam", freq=1, policy_noise=0.2,
+                       noise_clip=0.0),
+    "td3_per": dict(kind="td3", n_step=1, bs=32, optim="adam", freq=3, policy_noise=0.2,
+                    noise_clip=0.5, per=True),
+    "td3_nonoise": dict(kind="td3", n_step=1, bs=64, optim="adam", freq=2, policy_noise=0.0,
+                        noise_clip=0.5),
+}
+DDPG_TAU, DDPG_GAMMA, DDPG_INIT_SEED, DDPG_SAMPLE_SEED = 0.05, 0.97, 11, 8
+DDPG_NOISES = (("none", {}), ("gauss", dict(sigma=0.1)), ("gauss", dict(mu=0.05, sigma=0.3)),
+               ("ou", {}))
+
+
+def _np_state_arrays(prefix):
+    st = np.random.get_state()
+    return {prefix + "state_keys": st[1].copy(), prefix + "state_pos": np.array(st[2]),
+            prefix + "state_has_gauss": np.array(st[3]),
+            prefix + "state_cached": np.array(st[4])}
+
+
+def _ddpg_adds(rng):
+    """The add() stream of _dqn_adds (34 steps of all six envs, then 12 more of env 2 alone,
+    which wraps its 40-row sub-buffer; random episode ends) with DDPG_D-wide observations and
+    float actions [k, DDPG_A] in [-1, 1]."""
+    E, D, A = DQN_E, DDPG_D, DDPG_A
+    adds = []
+    for t in range(34 + 12):
+        ids = np.arange(E) if t < 34 else np.array([2])
+        k = len(ids)
+        done = rng.random(k) < 0.08
+        term = done & (rng.random(k) < 0.5)
+        adds.append(dict(ids=ids, obs=rng.standard_normal((k, D)).astype(np.float32),
+                         act=rng.uniform(-1.0, 1.0, (k, A)).astype(np.float32),
+                         rew=rng.standard_normal(k), terminated=term, truncated=done & ~term,
+                         obs_next=rng.standard_normal((k, D)).astype(np.float32)))
+    return adds
+
+
+def _named_arrays(prefix, module):
+    return {prefix + k: t.detach().numpy().copy() for k, t in module.named_parameters()}
+
+
+def _flat_params(policy, names):
+    """Every parameter of the networks ``names``, each followed by its target network's, in
+    named_parameters() order, as one f32 vector."""
+    mods = [getattr(policy, n + sfx) for n in names for sfx in ("", "_old")]
+    return np.concatenate([t.detach().numpy().ravel() for m in mods for t in m.parameters()])
+
+
+def gen_ddpg():
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.exploration import GaussianNoise, OUNoise
+    from tianshou.policy import DDPGPolicy, TD3Policy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import Actor, Critic
+    out = {}
+    # (a) exploration_noise
+    cases = []
+    for k, A in ((1, 1), (65, 6), (257, 17)):
+        for kind, kw in DDPG_NOISES:
+            noise = {"none": lambda: None, "gauss": lambda: GaussianNoise(**kw),
+                     "ou": lambda: OUNoise(**kw)}[kind]()
+            calls = 3 if kind == "ou" else 1
+            rng = np.random.default_rng(200 + len(cases))
+            policy = DDPGPolicy(None, None, None, None, exploration_noise=noise,
+                                action_scaling=False)
+            act = rng.uniform(-1.0, 1.0, (k, A)).astype(np.float32)  # the same for every call
+            seed = 700 + len(cases)
+            p = f"noise{len(cases)}_"
+            out[p + "act_in"] = act
+            np.random.seed(seed)
+            res = [policy.exploration_noise(act, Batch()) for c in range(calls)]
+            if kind == "none":  # handed back as it is: nothing to record
+                assert res[0] is act
+            else:
+                out[p + "act_out"] = np.stack(res)
+                assert out[p + "act_out"].dtype == np.float64
+            out.update(_np_state_arrays(p))
+            if kind == "ou":
+                out[p + "ou_x"] = np.array(noise._x, copy=True)
+            cases.append(dict(k=k, A=A, kind=kind, kw=kw, calls=calls, seed=seed))
+    out["noise_cfg"] = np.array(json.dumps(cases))
+
+    # (b) learn variants
+    E, S, D, A = DQN_E, DQN_S, DDPG_D, DDPG_A
+    adds = _ddpg_adds(np.random.default_rng(43))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+
+    def optim_of(kind, params):
+        if kind == "rms":
+            return torch.optim.RMSprop(params, lr=7e-4, eps=1e-5, alpha=0.99)
+        return torch.optim.Adam(params, lr=1e-3)
+
+    real_randn = torch.randn
+    for tag, v in DDPG_VARIANTS.items():
+        p = tag + "_"
+        if v.get("per"):
+            buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+        else:
+            buf = VectorReplayBuffer(E * S, E)
+        for a in adds:
+            buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                    buffer_ids=a["ids"])
+        torch.manual_seed(DDPG_INIT_SEED)
+        actor = Actor(Net(D, hidden_sizes=(16, 16)), (A,))
+        ncrit = 1 if v["kind"] == "ddpg" else 2
+        critics = [Critic(Net(D, A, hidden_sizes=(16, 16), concat=True)) for _ in range(ncrit)]
+        if v["kind"] == "ddpg":
+            names = ("actor", "critic")
+            policy = DDPGPolicy(actor, optim_of(v["optim"], actor.parameters()), critics[0],
+                                optim_of(v["optim"], critics[0].parameters()), tau=DDPG_TAU,
+                                gamma=DDPG_GAMMA, exploration_noise=None,
+                                estimation_step=v["n_step"], action_scaling=False)
+        else:
+            names = ("actor", "critic1", "critic2")
+            policy = TD3Policy(actor, optim_of(v["optim"], actor.parameters()), critics[0],
+                               optim_of(v["optim"], critics[0].parameters()), critics[1],
+                               optim_of(v["optim"], critics[1].parameters()), tau=DDPG_TAU,
+                               gamma=DDPG_GAMMA, exploration_noise=None,
+                               policy_noise=v["policy_noise"], update_actor_freq=v["freq"],
+                               noise_clip=v["noise_clip"], estimation_step=v["n_step"],
+                               action_scaling=False)
+        if tag in ("ddpg", "td3"):  # every variant of a kind starts from these weights
+            for name in names:
+                out.update(_named_arrays(f"{v['kind']}_init_{name}.", getattr(policy, name)))
+        if tag == "ddpg":
+            out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                np.asarray(buf.last_index)
+            # the recorded forward of utils.net.Actor's test
+            out["actor_fwd_obs"] = adds[0]["obs"]
+            out["actor_fwd_act"] = actor(adds[0]["obs"])[0].detach().numpy().copy()
+        process_fn, learn = policy.process_fn, policy.learn
+        seen, draws = [], []
+
+        def rec_randn(*a, **kw):
+            t = real_randn(*a, **kw)
+            draws.append(t.numpy().copy())
+            return t
+
+        def rec_process(batch, buffer, indices):
+            n0 = len(draws)
+            batch = process_fn(batch, buffer, indices)
+            seen.append(dict(indices=np.array(indices, copy=True),
+                             returns=batch.returns.detach().numpy().copy()))
+            assert len(draws) - n0 == (1 if v["kind"] == "td3" else 0)
+            if len(draws) > n0:
+                seen[-1]["randn"] = draws[-1]
+            if hasattr(batch, "weight"):
+                seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+            return batch
+
+        def rec_learn(batch, **kw):
+            with torch.no_grad():  # the critic at (obs, act) before the update: |Q|'s scale
+                seen[-1]["q_obs"] = getattr(policy, names[1])(batch.obs, batch.act) \
+                    .flatten().numpy().copy()
+            res = learn(batch, **kw)
+            seen[-1]["td"] = batch.weight.detach().numpy().copy()
+            return res
+
+        policy.process_fn, policy.learn = rec_process, rec_learn
+        np.random.seed(DDPG_SAMPLE_SEED)
+        torch.manual_seed(DDPG_SAMPLE_SEED)
+        torch.randn = rec_randn
+        try:
+            for u in range(6):
+                res = policy.update(v["bs"], buf)
+                row = seen[u]
+                for k, x in res.items():
+                    row[k.replace("/", "_")] = np.array(x)
+                row["params"] = _flat_params(policy, names)
+                if v["kind"] == "td3":
+                    row["cnt"], row["last"] = np.array(policy._cnt), \
+                        np.array(float(policy._last))
+                if v.get("per"):
+                    row["leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+        finally:
+            torch.randn = real_randn
+        for k in seen[0]:  # one array per quantity: the six updates stacked
+            out[p + k] = np.stack([row[k] for row in seen])
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=E, S=S, D=D, A=A, gamma=DDPG_GAMMA, tau=DDPG_TAU, hidden=[16, 16],
+        seed=DDPG_SAMPLE_SEED, variants=DDPG_VARIANTS,
+        nets=dict(ddpg=["actor", "critic"], td3=["actor", "critic1", "critic2"]))))
+
+    # (c) one collect with exploration noise
+    n_env, n_step, Dc, Ac, L, coef, sigma = 4, 60, 5, 2, 7, 0.05, 0.6
+    low, high = np.array([-2.0, -0.5], np.float32), np.array([1.0, 3.0], np.float32)
+
+    class CoupledSynthGymEnv(SynthGymEnv):
+        """SynthGymEnv with oracle.synth_env's action coupling and a non-symmetric Box."""
+
+        def __init__(self, e):
+            super().__init__(e, Dc, Ac, L, seed=9)
+            self.action_space = gym.spaces.Box(low, high, (Ac,), np.float32)
+
+        def step(self, action):
+            obs, rew, term, trunc, info = super().step(action)
+            a = np.asarray(action, np.float32).reshape(Ac)
+            ca = (np.float32(coef) * a[np.arange(Dc) % Ac]).astype(np.float32)
+            return (obs + ca).astype(np.float32), rew, term, trunc, info
+
+    envs = DummyVectorEnv([lambda e=e: CoupledSynthGymEnv(e) for e in range(n_env)])
+    seed = 1733
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    actor = Actor(Net(Dc, hidden_sizes=(16, 16)), (Ac,))
+    critic = Critic(Net(Dc, Ac, hidden_sizes=(16, 16), concat=True))
+    with torch.no_grad():
+        for t in actor.last.parameters():
+            t.zero_()
+    policy = DDPGPolicy(actor, torch.optim.Adam(actor.parameters(), lr=1e-3), critic,
+                        torch.optim.Adam(critic.parameters(), lr=1e-3),
+                        exploration_noise=GaussianNoise(sigma=sigma),
+                        action_space=envs.action_space[0], action_scaling=True,
+                        action_bound_method="clip")
+    buf = VectorReplayBuffer(n_env * 20, n_env)
+    c = Collector(policy, envs, buf, exploration_noise=True)
+    res = c.collect(n_step=n_step)
+    out.update(_stats_arrays("col_", res))
+    out.update(_buf_arrays("col_buf_", buf))
+    assert out["col_buf_act"].dtype == np.float64
+    assert (np.abs(out["col_buf_act"]) > 1.0).any()  # the clip of map_action binds
+    out.update(_np_state_arrays("col_"))
+    out["col_cfg"] = np.array(json.dumps(dict(
+        seed=seed, E=n_env, n_step=n_step, size=n_env * 20, D=Dc, A=Ac, L=L, env_seed=9,
+        act_coef=coef, sigma=sigma, low=low.tolist(), high=high.tolist())))
+    _save("ddpg.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
-                             "persist", "trainer", "a2c", "dqn", "dist_dqn"]
+                             "persist", "trainer", "a2c", "dqn", "dist_dqn", "ddpg"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -1706,6 +1960,6 @@ if __name__ == "__main__":
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
                  persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn,
-                 dist_dqn=gen_dist_dqn)
+                 dist_dqn=gen_dist_dqn, ddpg=gen_ddpg)
     for w in which:
         table[w]()
