@@ -873,6 +873,48 @@ int tsrl_neg_mean_fwd_bwd(const float* q, int64_t b, float* grad, double* partia
                           void* stream);
 int tsrl_act_noise(const float* act, const double* noise, int64_t n, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * SACPolicy (tianshou/policy/modelfree/sac.py), csrc/sac.hip.  One launch each unless noted;
+ * all tensors f32; eps32 = 2^-23 (np.finfo(np.float32).eps).  alpha and log_alpha are pointers
+ * to one device f32 each, read by the kernel: the temperature changes inside a replayed graph.
+ * tsrl_sac_sample_fwd: forward's sample and log-probability (sac.py:117-128) over mu, sigma,
+ *   eps, act [b, A] and log_prob [b], any A >= 1.  u = fl(mu + fl(eps * sigma)) (no FMA: torch's
+ *   rsample bit for bit), act = tanhf(u), log_prob[r] = sum_j [-(u -
+ *   mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi)] - sum_j log(fl(fl(1 - fl(act^2)) + eps32)).
+ *   Every term is evaluated in f32 as torch evaluates it and the terms of a row are summed in
+ *   f64 in index order; a saturated action contributes exactly log(eps32), never -inf.  eps
+ *   NULL is deterministic_eval: act = tanh(mu), the log-probability taken at mu.
+ * tsrl_sac_sample_bwd: its analytic gradient.  With one_m = 1 - act^2 and c = 2 act one_m /
+ *   (one_m + eps32): g_mu = g_act one_m + g_logp c, g_sigma = eps g_mu - g_logp / sigma (eps
+ *   NULL: eps = 0).  g_act [b, A] or g_logp [b] may be NULL (that output unused), not both.
+ *   The Gaussian term's gradients through the sample and through loc cancel; they are not
+ *   computed.
+ * tsrl_sac_target: _target_q (sac.py:141-144): out = fl(min(q1, q2) - fl(alpha * log_prob)),
+ *   all [b]; a NaN in q1 or q2 is handed through as torch.min hands it through.
+ * tsrl_sac_actor_loss_fwd_bwd: sac.py:162-165 and 171-173.  loss[0] = mean(fl(fl(alpha *
+ *   log_prob) - min(q1, q2))), g_logp[r] = fl(alpha * (1 / b)), and -1 / b goes to the smaller
+ *   critic's g_q.  torch's derivative of min(self, other) is where(self == other, grad / 2,
+ *   grad) with the side whose operand is larger then zeroed: a tie q1 == q2 gives each critic
+ *   -1 / (2 b), and a NaN row (every comparison false) gives both the whole -1 / b.  With
+ *   log_alpha: loss[1] = -log_alpha mean(log_prob + target_entropy) and g_log_alpha[0] =
+ *   -mean(fl(log_prob + (float)target_entropy)); log_alpha NULL leaves loss[1] and g_log_alpha
+ *   untouched (g_log_alpha may then be NULL).  The sums are f64 in the fixed order of
+ *   tsrl_q_mse_fwd_bwd.  partials: 2 * tsrl_ddpg_num_partials(b) doubles, read and written only
+ *   when that count is > 1 (b > 256: a second one-lane launch folds them), else may be NULL.
+ * ------------------------------------------------------------------------------- */
+int tsrl_sac_sample_fwd(const float* mu, const float* sigma, const float* eps, int64_t b,
+                        int64_t A, float* act, float* log_prob, void* stream);
+int tsrl_sac_sample_bwd(const float* sigma, const float* eps, const float* act,
+                        const float* g_act, const float* g_logp, int64_t b, int64_t A,
+                        float* g_mu, float* g_sigma, void* stream);
+int tsrl_sac_target(const float* q1, const float* q2, const float* log_prob, const float* alpha,
+                    int64_t b, float* out, void* stream);
+int tsrl_sac_actor_loss_fwd_bwd(const float* q1, const float* q2, const float* log_prob,
+                                const float* alpha, const float* log_alpha,
+                                double target_entropy, int64_t b, float* g_q1, float* g_q2,
+                                float* g_logp, double* partials, float* loss,
+                                float* g_log_alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

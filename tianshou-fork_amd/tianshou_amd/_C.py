@@ -226,6 +226,11 @@ _SIGS = {
     "tsrl_q_mse_fwd_bwd": ([_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_neg_mean_fwd_bwd": ([_p, _i64, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_act_noise": ([_p, _p, _i64, _p, _p], ctypes.c_int),
+    "tsrl_sac_sample_fwd": ([_p, _p, _p, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_sac_sample_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_sac_target": ([_p, _p, _p, _p, _i64, _p, _p], ctypes.c_int),
+    "tsrl_sac_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _d, _i64, _p, _p, _p, _p, _p, _p, _p],
+                                    ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

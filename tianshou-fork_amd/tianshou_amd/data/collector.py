@@ -674,9 +674,12 @@ class Collector:
                 # episodes' statistics of the steps so far before the ring laps them
                 ep_stats.append(self._episode_stats(written))
                 written = []
+            # eager_collect_step: a policy whose forward draws on the host side of the launch
+            # (SACPolicy._rsample_noise) is not captured
             if (n_step is not None and self.graph_steps and not random and kk == N
                     and kk == buf.buffer_num and buf._ring.uniform_rel() is not None
-                    and eager_steps > 0 and not self._noise_active()):
+                    and eager_steps > 0 and not self._noise_active()
+                    and not getattr(self.policy, "eager_collect_step", False)):
                 n_left = min(-(-(n_step - step_count) // N), S - len(written))
                 done_steps = self._replay_steps(no_grad, n_left, written)
                 step_count += done_steps * N

@@ -9,6 +9,7 @@ from tianshou_amd.policy.c51 import C51Policy
 from tianshou_amd.policy.qrdqn import QRDQNPolicy
 from tianshou_amd.policy.ddpg import DDPGPolicy
 from tianshou_amd.policy.td3 import TD3Policy
+from tianshou_amd.policy.sac import SACPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
-           "DQNPolicy", "C51Policy", "QRDQNPolicy", "DDPGPolicy", "TD3Policy"]
+           "DQNPolicy", "C51Policy", "QRDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy"]

@@ -17,9 +17,10 @@ What stays on torch: a network with module buffers or another optimiser (``soft_
 ``optim.step()`` for that network; no graph replay), and ``fused = False`` -- the reference's
 op sequence on the GPU, kept as the comparison leg of tools/ddpg_update_bench.py.
 
-Not built: SAC, REDQ, an OffpolicyTrainer, data-parallel updates, a fused act kernel for
-deterministic actors (the Collector keeps such a policy on its eager device step) and reward
-normalisation (compute_nstep_return asserts against it).
+SACPolicy (policy/sac.py) builds on the same hooks.  Not built: REDQ, an OffpolicyTrainer,
+data-parallel updates, a fused act kernel for deterministic actors (the Collector keeps such a
+policy on its eager device step) and reward normalisation (compute_nstep_return asserts
+against it).
 """
 import warnings
 from copy import deepcopy
@@ -169,7 +170,14 @@ class DDPGPolicy(BasePolicy):
 
     GRAPH_LEARN_MAX_ROWS = 65536
     _critic_names: Tuple[str, ...] = ("critic",)
-    _sync_order: Tuple[str, ...] = ("actor", "critic")  # ddpg.py:119-120
+    # the networks with a target copy, in sync_weight's order (ddpg.py:119-120)
+    _sync_order: Tuple[str, ...] = ("actor", "critic")
+
+    @property
+    def _optim_order(self) -> Tuple[str, ...]:
+        """The networks with an optimiser of their own.  Here and in TD3Policy every one of
+        them has a target copy too; SACPolicy's actor has none."""
+        return self._sync_order
 
     def __init__(self, actor: Optional[torch.nn.Module],
                  actor_optim: Optional[torch.optim.Optimizer],
@@ -226,7 +234,7 @@ class DDPGPolicy(BasePolicy):
     def train(self, mode: bool = True) -> "DDPGPolicy":
         """ddpg.py:110-115: the target networks stay in eval mode."""
         self.training = mode
-        for name in self._sync_order:
+        for name in self._optim_order:
             getattr(self, name).train(mode)
         return self
 
@@ -238,11 +246,11 @@ class DDPGPolicy(BasePolicy):
     def _bind(self, name: str) -> Optional[FlatAdam]:
         """The flat gradient / optimiser storage of network ``name`` when its optimiser is a
         plain Adam or RMSprop over exactly its parameters (None otherwise: torch's step and
-        BasePolicy.soft_update run for it).  Its target network's parameters then become views
-        into a second flat buffer laid out as the first."""
+        BasePolicy.soft_update run for it).  Its target network's parameters, where it has one,
+        then become views into a second flat buffer laid out as the first."""
         if not (self.fused and self.fused_adam and self._on_device()):
             return None
-        net, old = getattr(self, name), getattr(self, name + "_old")
+        net, old = getattr(self, name), getattr(self, name + "_old", None)
         st = self._flats.get(name)
         if st is None:
             st = self._flats[name] = dict(fa=FlatAdam(net.parameters()), old=None, src=None)
@@ -250,7 +258,7 @@ class DDPGPolicy(BasePolicy):
         if not fa.bind_adam(getattr(self, name + "_optim")):
             st["old"] = st["src"] = None
             return None
-        if not self._old_is_flat(st, old):
+        if old is not None and not self._old_is_flat(st, old):
             src = fa.flat_param
             flat_old = torch.empty_like(src)
             o = 0
@@ -282,6 +290,16 @@ class DDPGPolicy(BasePolicy):
                 and next(net.buffers(), None) is None:
             return st["old"], st["fa"].flat_param
         return None
+
+    def _flat_ready(self, name: str) -> bool:
+        """Network ``name`` steps and (where it has a target copy) syncs on flat storage alone:
+        what a captured update needs of every network."""
+        if hasattr(self, name + "_old"):
+            return self._flat_pair(name) is not None
+        st = self._flats.get(name)
+        return bool(self.fused and st is not None
+                    and st["fa"].adam_bound(getattr(self, name + "_optim"))
+                    and next(getattr(self, name).buffers(), None) is None)
 
     def sync_weight(self) -> None:
         """ddpg.py:117-120 (td3.py:93-96): every network with flat storage in one
@@ -365,6 +383,16 @@ class DDPGPolicy(BasePolicy):
     def _result(self, losses: List[float], did_actor: bool) -> Dict[str, float]:
         return {"loss/actor": losses[-1], "loss/critic": losses[0]}
 
+    def _loss_slots(self) -> int:
+        """Length of the device vector that the update's one host read brings back: one loss
+        per critic, then the actor's."""
+        return len(self._critic_names) + 1
+
+    def _learn_draws(self, act: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """Random draws of one fused update, made before it runs: further static inputs of a
+        captured graph, handed to _step after its other arguments.  None here."""
+        return ()
+
     def _learn_torch(self, batch: Batch, do_actor: bool):
         """The reference's op sequence as written (ddpg.py:184-194, td3.py:111-128), on
         whatever device the networks live on; returns (losses, per-row vector)."""
@@ -394,7 +422,7 @@ class DDPGPolicy(BasePolicy):
         if not (self.fused and self._on_device()):
             loss, td = self._learn_torch(batch, do_actor)
         else:
-            fas = {name: self._bind(name) for name in self._sync_order}
+            fas = {name: self._bind(name) for name in self._optim_order}
             dev = next(self.actor.parameters()).device
             n = len(batch.returns)
             weight = batch.get("weight", None)
@@ -403,16 +431,17 @@ class DDPGPolicy(BasePolicy):
                 .contiguous()
             returns = _f32_rows(batch.returns, dev, n)
             w = None if weight is None else _f32_rows(weight, dev, n)
+            draws = self._learn_draws(act)
             out = None
             if all(fa is not None for fa in fas.values()):
                 for fa in fas.values():
                     fa.set_lr()
                 if self._warm and self._graph_ok(obs, n):
-                    out = self._graph_step(fas, obs, act, returns, w, do_actor)
+                    out = self._graph_step(fas, obs, act, returns, w, do_actor, *draws)
             if out is None:
-                loss = torch.empty(nc + 1, dtype=torch.float32, device=dev)
+                loss = torch.empty(self._loss_slots(), dtype=torch.float32, device=dev)
                 td = torch.empty(n, dtype=torch.float32, device=dev)
-                self._step(fas, obs, act, returns, w, do_actor, td, loss)
+                self._step(fas, obs, act, returns, w, do_actor, td, loss, *draws)
                 out = (loss, td)
             loss, td = out
             self._warm = True
@@ -476,52 +505,57 @@ class DDPGPolicy(BasePolicy):
     def _graph_ok(self, obs, n: int) -> bool:
         if self._graph_failed or not isinstance(obs, torch.Tensor) or not obs.is_cuda:
             return False
-        return self._use_graph(n) and all(self._flat_pair(name) is not None
-                                          for name in self._sync_order)
+        return self._use_graph(n) and all(self._flat_ready(name) for name in self._optim_order)
 
     def _capture(self, graph):
         """The capture context of a learn graph (utils.capture.graph_capture)."""
         return graph_capture(graph)
 
-    def _graph_step(self, fas: Dict[str, FlatAdam], obs, act, returns, weight, do_actor: bool):
-        """One update replayed from a HIP graph captured once per (batch size, observation
-        shape and dtype, action shape, weight present, step kind, flat addresses); static
-        copies of obs / act / returns / weight feed it, the losses and the per-row vector come
-        out of static outputs.  None if the capture failed (this and every later update then
-        run eagerly)."""
+    def _graph_addr(self, fas: Dict[str, FlatAdam]) -> tuple:
+        """The flat addresses a captured update is tied to."""
         addr = []
-        for name in self._sync_order:
+        for name in self._optim_order:
             fa = fas[name]
             fa.bind_grads()
-            addr.append((fa.flat_grad.data_ptr(), self._flats[name]["old"].data_ptr(),
+            old = self._flats[name]["old"]
+            addr.append((fa.flat_grad.data_ptr(), None if old is None else old.data_ptr(),
                          tuple(p.data_ptr() for p in fa.params)))
-        addr = tuple(addr)
+        return tuple(addr)
+
+    def _graph_step(self, fas: Dict[str, FlatAdam], obs, act, returns, weight, do_actor: bool,
+                    *draws: torch.Tensor):
+        """One update replayed from a HIP graph captured once per (batch size, observation
+        shape and dtype, action shape, weight present, step kind, draws, flat addresses);
+        static copies of obs / act / returns / weight / the draws feed it, the losses and the
+        per-row vector come out of static outputs.  None if the capture failed (this and every
+        later update then run eagerly)."""
+        addr = self._graph_addr(fas)
         if self._learn_graphs and next(iter(self._learn_graphs.values()))["addr"] != addr:
             self._learn_graphs.clear()
         key = (len(returns), tuple(obs.shape), obs.dtype, tuple(act.shape), weight is not None,
-               bool(do_actor))
+               *(tuple(d.shape) for d in draws), bool(do_actor))
         st = self._learn_graphs.get(key)
         if st is None:
             static = [obs.clone(), act.clone(), returns.clone(),
                       None if weight is None else weight.clone()]
+            static_draws = [d.clone() for d in draws]
             td = torch.empty(len(returns), dtype=torch.float32, device=act.device)
-            loss = torch.zeros(len(self._critic_names) + 1, dtype=torch.float32,
-                               device=act.device)
+            loss = torch.zeros(self._loss_slots(), dtype=torch.float32, device=act.device)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             try:
                 with self._capture(graph):
-                    self._step(fas, *static, do_actor, td, loss)
+                    self._step(fas, *static, do_actor, td, loss, *static_draws)
             except RuntimeError as err:
                 warnings.warn(f"learn-graph capture failed, running updates eagerly: {err}")
                 self._graph_failed = True
                 self._learn_graphs.clear()
                 torch.cuda.synchronize()
                 return None
-            st = self._learn_graphs[key] = dict(addr=addr, graph=graph, static=static, td=td,
-                                                loss=loss)
+            st = self._learn_graphs[key] = dict(addr=addr, graph=graph,
+                                                static=static + static_draws, td=td, loss=loss)
         else:
-            for d, a in zip(st["static"], (obs, act, returns, weight)):
+            for d, a in zip(st["static"], (obs, act, returns, weight, *draws)):
                 if d is not None:
                     d.copy_(a)
         st["graph"].replay()

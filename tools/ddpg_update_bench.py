@@ -1,12 +1,15 @@
-"""Time DDPGPolicy.update() and TD3Policy.update() (sample + process_fn + learn +
-post_process_fn) on one filled VectorReplayBuffer: HIP events around each of --updates updates
-after --warmup.
+"""Time DDPGPolicy.update(), TD3Policy.update() and SACPolicy.update() (sample + process_fn +
+learn + post_process_fn) on one filled VectorReplayBuffer: HIP events around each of --updates
+updates after --warmup.
 
-    python tools/ddpg_update_bench.py              # both policies, both shapes, three legs
+    python tools/ddpg_update_bench.py              # DDPG and TD3, both shapes, three legs
+    python tools/ddpg_update_bench.py --policies sac
 
 Shapes: "d17" obs 17 / act 6 (examples/mujoco/mujoco_td3.py on HalfCheetah) and "d376" obs 376 /
 act 17 (Humanoid), hidden (256, 256), batch 256, Adam, n_step 1; TD3 with its default
-update_actor_freq 2, so its mean covers both step kinds.
+update_actor_freq 2, so its mean covers both step kinds; SAC (examples/mujoco/mujoco_sac.py)
+with ActorProb(unbounded, conditioned_sigma) and the automatic temperature (target_entropy =
+-act, Adam on log_alpha).
 Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), "eager"
 (graph_learn=False: the fused kernels and the flat Adam passes launched eagerly) and "torch"
 (fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
@@ -34,8 +37,8 @@ ap.add_argument("--torch-runs", type=int, default=3)
 args = ap.parse_args()
 
 from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
-from tianshou_amd.policy import DDPGPolicy, TD3Policy  # noqa: E402
-from tianshou_amd.utils.net import Actor, Critic, Net  # noqa: E402
+from tianshou_amd.policy import DDPGPolicy, SACPolicy, TD3Policy  # noqa: E402
+from tianshou_amd.utils.net import Actor, ActorProb, Critic, Net  # noqa: E402
 
 dev = torch.device("cuda", 0)
 CONFIGS = {
@@ -67,7 +70,11 @@ def fill(cfg):
 def make_policy(kind, cfg, leg):
     torch.manual_seed(0)
     D, A = cfg["D"], cfg["A"]
-    actor = Actor(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev).to(dev)
+    if kind == "sac":
+        actor = ActorProb(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev,
+                          unbounded=True, conditioned_sigma=True).to(dev)
+    else:
+        actor = Actor(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev).to(dev)
     critics = [Critic(Net(D, A, hidden_sizes=HIDDEN, concat=True, device=dev), device=dev)
                .to(dev) for _ in range(1 if kind == "ddpg" else 2)]
     a_opt = torch.optim.Adam(actor.parameters(), lr=3e-4)
@@ -76,6 +83,11 @@ def make_policy(kind, cfg, leg):
               action_scaling=False)
     if kind == "ddpg":
         policy = DDPGPolicy(actor, a_opt, critics[0], c_opt[0], **kw)
+    elif kind == "sac":
+        log_alpha = torch.zeros(1, requires_grad=True, device=dev)
+        alpha = (-float(A), log_alpha, torch.optim.Adam([log_alpha], lr=3e-4))
+        policy = SACPolicy(actor, a_opt, critics[0], c_opt[0], critics[1], c_opt[1],
+                           alpha=alpha, **kw)
     else:
         policy = TD3Policy(actor, a_opt, critics[0], c_opt[0], critics[1], c_opt[1], **kw)
     policy = policy.to(dev)
@@ -114,5 +126,5 @@ for kind in args.policies.split(","):
                     "update_ms_max": round(float(ms.max()), 4),
                     "graphs": len(policy._learn_graphs),
                     "flat_optimiser": bool(policy._flats) and all(
-                        policy._flat_pair(n) is not None for n in policy._sync_order),
+                        policy._flat_ready(n) for n in policy._optim_order),
                     "last": {k: round(float(v), 6) for k, v in last.items()}}), flush=True)

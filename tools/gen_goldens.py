@@ -1762,6 +1762,23 @@ def _flat_params(policy, names):
     return np.concatenate([t.detach().numpy().ravel() for m in mods for t in m.parameters()])
 
 
+def _coupled_env(Dc, Ac, L, coef, low, high):
+    class CoupledSynthGymEnv(SynthGymEnv):
+        """SynthGymEnv with oracle.synth_env's action coupling and a non-symmetric Box."""
+
+        def __init__(self, e):
+            super().__init__(e, Dc, Ac, L, seed=9)
+            self.action_space = gym.spaces.Box(low, high, (Ac,), np.float32)
+
+        def step(self, action):
+            obs, rew, term, trunc, info = super().step(action)
+            a = np.asarray(action, np.float32).reshape(Ac)
+            ca = (np.float32(coef) * a[np.arange(Dc) % Ac]).astype(np.float32)
+            return (obs + ca).astype(np.float32), rew, term, trunc, info
+
+    return CoupledSynthGymEnv
+
+
 def gen_ddpg():
     from tianshou.data import PrioritizedVectorReplayBuffer
     from tianshou.exploration import GaussianNoise, OUNoise
@@ -1906,19 +1923,7 @@ def gen_ddpg():
     n_env, n_step, Dc, Ac, L, coef, sigma = 4, 60, 5, 2, 7, 0.05, 0.6
     low, high = np.array([-2.0, -0.5], np.float32), np.array([1.0, 3.0], np.float32)
 
-    class CoupledSynthGymEnv(SynthGymEnv):
-        """SynthGymEnv with oracle.synth_env's action coupling and a non-symmetric Box."""
-
-        def __init__(self, e):
-            super().__init__(e, Dc, Ac, L, seed=9)
-            self.action_space = gym.spaces.Box(low, high, (Ac,), np.float32)
-
-        def step(self, action):
-            obs, rew, term, trunc, info = super().step(action)
-            a = np.asarray(action, np.float32).reshape(Ac)
-            ca = (np.float32(coef) * a[np.arange(Dc) % Ac]).astype(np.float32)
-            return (obs + ca).astype(np.float32), rew, term, trunc, info
-
+    CoupledSynthGymEnv = _coupled_env(Dc, Ac, L, coef, low, high)
     envs = DummyVectorEnv([lambda e=e: CoupledSynthGymEnv(e) for e in range(n_env)])
     seed = 1733
     np.random.seed(seed)
@@ -1947,12 +1952,237 @@ def gen_ddpg():
     _save("ddpg.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 23. SACPolicy (tianshou/policy/modelfree/sac.py) over gen_ddpg's add() stream:
+#     (a) one forward in eval mode (deterministic) and one in training mode;
+#     (b) six update() calls per variant.  torch.distributions.normal._standard_normal, the
+#         function rsample calls, is replaced by a recorder: a device generator cannot reproduce
+#         the CPU stream.  It hands back (and records) clamp(draw, -2, 2), which keeps the tanh
+#         correction log(1 - a^2 + eps32) well conditioned in f32.  An update draws twice, each
+#         [batch, A]: in process_fn, then in learn;
+#     (c) one Collector.collect in training mode over gen_ddpg's coupled env, the last layers of
+#         mu and sigma zeroed: mu = 0 and sigma = 1 exactly whatever GEMM runs, so the stored
+#         action is tanh(draw).
+#     Asserted on the reference alone: min(1 - act^2) >= 0.02 over every recorded forward, and
+#     min |Q1 - Q2| >= 1e-4 at the sampled action of every learn (the route of the min's gradient
+#     cannot flip with the GEMM).  A variant that misses one gets another "seed", not a bound.
+# --------------------------------------------------------------------------------------
+SAC_VARIANTS = {
+    "sac": dict(init="sac", auto=False, n_step=1, bs=64, optim="adam"),
+    "sac_auto": dict(init="sac", auto=True, n_step=3, bs=65, optim="adam"),
+    "sac_per": dict(init="sac", auto=True, n_step=1, bs=32, optim="adam", per=True),
+    "sac_rms": dict(init="sac", auto=True, n_step=1, bs=64, optim="rms"),
+    "sac_bounded": dict(init="sac_bounded", auto=False, n_step=1, bs=64, optim="adam",
+                        bounded=True),
+}
+SAC_ALPHA, SAC_ALPHA_LR = 0.2, 3e-3
+SAC_NETS = ["actor", "critic1", "critic2"]
+
+
+def _sac_flat_params(policy):
+    """actor, critic1, critic1_old, critic2, critic2_old in named_parameters() order."""
+    mods = [policy.actor, policy.critic1, policy.critic1_old, policy.critic2, policy.critic2_old]
+    return np.concatenate([t.detach().numpy().ravel() for m in mods for t in m.parameters()])
+
+
+def gen_sac():
+    import torch.distributions.normal as tdn
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import SACPolicy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import ActorProb, Critic
+    out = {}
+    E, S, D, A = DQN_E, DQN_S, DDPG_D, DDPG_A
+    adds = _ddpg_adds(np.random.default_rng(43))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    real_normal = tdn._standard_normal
+    draws = []
+
+    def rec_normal(shape, dtype, device):
+        t = real_normal(shape, dtype=dtype, device=device).clamp(-2.0, 2.0)
+        draws.append(t.numpy().copy())
+        return t
+
+    def optim_of(kind, params, lr=None):
+        if kind == "rms":
+            return torch.optim.RMSprop(params, lr=lr or 7e-4, eps=1e-5, alpha=0.99)
+        return torch.optim.Adam(params, lr=lr or 1e-3)
+
+    tdn._standard_normal = rec_normal
+    try:
+        for tag, v in SAC_VARIANTS.items():
+            p = tag + "_"
+            if v.get("per"):
+                buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+            else:
+                buf = VectorReplayBuffer(E * S, E)
+            for a in adds:
+                buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                        buffer_ids=a["ids"])
+            torch.manual_seed(DDPG_INIT_SEED)
+            bounded = bool(v.get("bounded"))
+            actor = ActorProb(Net(D, hidden_sizes=(16, 16)), (A,), unbounded=not bounded,
+                              conditioned_sigma=not bounded)
+            critics = [Critic(Net(D, A, hidden_sizes=(16, 16), concat=True)) for _ in range(2)]
+            alpha = SAC_ALPHA
+            if v["auto"]:
+                log_alpha = torch.zeros(1, requires_grad=True)
+                alpha = (-float(A), log_alpha, optim_of(v["optim"], [log_alpha], SAC_ALPHA_LR))
+            policy = SACPolicy(actor, optim_of(v["optim"], actor.parameters()), critics[0],
+                               optim_of(v["optim"], critics[0].parameters()), critics[1],
+                               optim_of(v["optim"], critics[1].parameters()), tau=DDPG_TAU,
+                               gamma=DDPG_GAMMA, alpha=alpha, estimation_step=v["n_step"],
+                               action_scaling=False)
+            if tag == v["init"]:  # every variant of an actor kind starts from these weights
+                for name in SAC_NETS:
+                    out.update(_named_arrays(f"{tag}_init_{name}.", getattr(policy, name)))
+            forward, process_fn, learn = policy.forward, policy.process_fn, policy.learn
+            seen, fwd, q_calls = [], [], {1: [], 2: []}
+            min_one_m = [np.inf]
+
+            def rec_forward(batch, *a, **kw):
+                res = forward(batch, *a, **kw)
+                act = res.act.detach().numpy().astype(np.float64)
+                min_one_m[0] = min(min_one_m[0], float((1.0 - act * act).min()))
+                fwd.append(res)
+                return res
+
+            policy.forward = rec_forward
+            hooks = [getattr(policy, f"critic{i}").register_forward_hook(
+                lambda m, a, o, i=i: q_calls[i].append(o.detach().flatten().numpy().copy()))
+                for i in (1, 2)]
+            if tag == "sac":
+                out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                    np.asarray(buf.last_index)
+                torch.manual_seed(DDPG_SAMPLE_SEED + 1)
+                obs = adds[0]["obs"]
+                out["fwd_obs"] = obs
+                for mode in ("eval", "train"):
+                    policy.train(mode == "train")
+                    n0 = len(draws)
+                    with torch.no_grad():
+                        res = policy(Batch(obs=obs, info={}))
+                    assert len(draws) - n0 == (mode == "train")
+                    out[f"fwd_{mode}_act"] = res.act.numpy().copy()
+                    out[f"fwd_{mode}_log_prob"] = res.log_prob.numpy().copy()
+                    for i, name in enumerate(("mu", "sigma")):
+                        out[f"fwd_{mode}_{name}"] = res.logits[i].numpy().copy()
+                out["fwd_train_eps"] = draws[-1]
+                np.testing.assert_allclose(out["fwd_eval_act"], np.tanh(
+                    out["fwd_eval_mu"].astype(np.float64)), rtol=3e-7)
+            policy.train()
+
+            def rec_process(batch, buffer, indices):
+                n0 = len(draws)
+                batch = process_fn(batch, buffer, indices)
+                assert len(draws) - n0 == 1 and draws[-1].shape == (v["bs"], A)
+                seen.append(dict(indices=np.array(indices, copy=True), eps_target=draws[-1],
+                                 returns=batch.returns.detach().numpy().copy()))
+                if hasattr(batch, "weight"):
+                    seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+                return batch
+
+            def rec_learn(batch, **kw):
+                n0, f0 = len(draws), len(fwd)
+                q0 = len(q_calls[1])
+                a_in = policy._alpha
+                seen[-1]["alpha_in"] = np.array(float(a_in), np.float32)
+                res = learn(batch, **kw)
+                assert len(draws) - n0 == 1 and len(fwd) - f0 == 1
+                assert len(q_calls[1]) - q0 == 2 and len(q_calls[2]) - q0 == 2
+                row = seen[-1]
+                row["eps_learn"] = draws[-1]
+                row["log_prob"] = fwd[-1].log_prob.detach().numpy().reshape(-1).copy()
+                row["q1a"], row["q2a"] = q_calls[1][-1], q_calls[2][-1]
+                assert np.abs(row["q1a"].astype(np.float64) - row["q2a"]).min() >= 1e-4, \
+                    (tag, len(seen), np.abs(row["q1a"] - row["q2a"]).min())
+                row["td"] = batch.weight.detach().numpy().copy()
+                return res
+
+            policy.process_fn, policy.learn = rec_process, rec_learn
+            np.random.seed(v.get("seed", DDPG_SAMPLE_SEED))
+            torch.manual_seed(v.get("seed", DDPG_SAMPLE_SEED))
+            for u in range(6):
+                res = policy.update(v["bs"], buf)
+                row = seen[u]
+                assert set(res) == {"loss/actor", "loss/critic1", "loss/critic2"} | (
+                    {"loss/alpha", "alpha"} if v["auto"] else set())
+                for k, x in res.items():
+                    row[k.replace("/", "_")] = np.array(x)
+                row["params"] = _sac_flat_params(policy)
+                if v["auto"]:
+                    row["log_alpha"] = policy._log_alpha.detach().numpy().copy()
+                if v.get("per"):
+                    row["leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+            for h in hooks:
+                h.remove()
+            assert min_one_m[0] >= 0.02, (tag, min_one_m[0])
+            print(tag, "min(1 - act^2)", min_one_m[0], "min|Q1 - Q2|",
+                  min(float(np.abs(r["q1a"] - r["q2a"]).min()) for r in seen))
+            for k in seen[0]:  # one array per quantity: the six updates stacked
+                out[p + k] = np.stack([row[k] for row in seen])
+            if v.get("per"):
+                out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                    np.array(buf._min_prio)
+        out["learn_cfg"] = np.array(json.dumps(dict(
+            E=E, S=S, D=D, A=A, gamma=DDPG_GAMMA, tau=DDPG_TAU, hidden=[16, 16],
+            seed=DDPG_SAMPLE_SEED, alpha=SAC_ALPHA, alpha_lr=SAC_ALPHA_LR,
+            target_entropy=-float(A), variants=SAC_VARIANTS, nets=SAC_NETS)))
+
+        # (c) one collect in training mode
+        n_env, n_step, Dc, Ac, L, coef = 4, 60, 5, 2, 7, 0.05
+        low, high = np.array([-2.0, -0.5], np.float32), np.array([1.0, 3.0], np.float32)
+        env_cls = _coupled_env(Dc, Ac, L, coef, low, high)
+        envs = DummyVectorEnv([lambda e=e: env_cls(e) for e in range(n_env)])
+        seed = 1733
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        actor = ActorProb(Net(Dc, hidden_sizes=(16, 16)), (Ac,), unbounded=True,
+                          conditioned_sigma=True)
+        critics = [Critic(Net(Dc, Ac, hidden_sizes=(16, 16), concat=True)) for _ in range(2)]
+        with torch.no_grad():
+            for head in (actor.mu, actor.sigma):
+                for t in list(head.parameters())[-2:]:
+                    t.zero_()
+        policy = SACPolicy(actor, torch.optim.Adam(actor.parameters(), lr=1e-3), critics[0],
+                           torch.optim.Adam(critics[0].parameters(), lr=1e-3), critics[1],
+                           torch.optim.Adam(critics[1].parameters(), lr=1e-3),
+                           action_space=envs.action_space[0], action_scaling=True,
+                           action_bound_method="clip")
+        policy.train()
+        buf = VectorReplayBuffer(n_env * 20, n_env)
+        c = Collector(policy, envs, buf)
+        n0 = len(draws)
+        res = c.collect(n_step=n_step)
+        col_draws = np.stack(draws[n0:])
+        assert col_draws.shape == (n_step // n_env, n_env, Ac)
+        out["col_eps"] = col_draws
+        out.update(_stats_arrays("col_", res))
+        out.update(_buf_arrays("col_buf_", buf))
+    finally:
+        tdn._standard_normal = real_normal
+    act = out["col_buf_act"]
+    assert act.dtype == np.float32
+    # the stored action is tanh(draw): row (env e, step t) of the buffer is sub-ring e, slot t
+    want = np.tanh(col_draws.astype(np.float64)).transpose(1, 0, 2).reshape(n_env, -1, Ac)
+    got = act.reshape(n_env, 20, Ac)[:, :n_step // n_env].astype(np.float64)
+    ulp = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
+    assert (np.abs(got - want) <= 2.0 * ulp).all(), float((np.abs(got - want) / ulp).max())
+    assert float((1.0 - got * got).min()) >= 0.02
+    out["col_cfg"] = np.array(json.dumps(dict(
+        seed=seed, E=n_env, n_step=n_step, size=n_env * 20, D=Dc, A=Ac, L=L, env_seed=9,
+        act_coef=coef, low=low.tolist(), high=high.tolist())))
+    _save("sac.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
-                             "persist", "trainer", "a2c", "dqn", "dist_dqn", "ddpg"]
+                             "persist", "trainer", "a2c", "dqn", "dist_dqn", "ddpg", "sac"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -1960,6 +2190,6 @@ if __name__ == "__main__":
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
                  persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn,
-                 dist_dqn=gen_dist_dqn, ddpg=gen_ddpg)
+                 dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac)
     for w in which:
         table[w]()
