@@ -915,6 +915,47 @@ int tsrl_sac_actor_loss_fwd_bwd(const float* q1, const float* q2, const float* l
                                 float* g_logp, double* partials, float* loss,
                                 float* g_log_alpha, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * DiscreteSACPolicy (tianshou/policy/modelfree/discrete_sac.py), csrc/dsac.hip.  logits, q1, q2
+ * and their gradients are row-major [b, num_actions] f32, any num_actions >= 1; alpha and
+ * log_alpha are pointers to one device f32 each, read by the kernel (the temperature changes
+ * inside a replayed graph); b == 0 launches nothing.  Per row, in f64 on the f32 inputs:
+ *   m = max_j l_j, S = sum_j exp(l_j - m), lp_j = l_j - m - log S, p_j = exp(lp_j),
+ *   H = -sum_j p_j lp_j (a term with p_j == 0 contributes exactly 0),
+ *   qm_j = min(q1_j, q2_j) (a NaN handed through as torch.min does), V = sum_j p_j qm_j
+ * -- Categorical(logits=l)'s normalisation, .probs and .entropy() for finite logits, whether l
+ * are raw scores or an actor's softmax output fed in as logits.  A -inf logit is out of scope
+ * (its p_j lp_j is NaN here, torch clamps it).  A group of lanes, the power of two >=
+ * num_actions capped at 64, shares a row; past 64 actions the group loops.
+ * tsrl_dsac_target: _target_q after the three forwards (:93-97): out[r] = (float)(V + alpha H).
+ * tsrl_dsac_q_loss_fwd_bwd: both critics' losses (:108-124).  td_k = q_k[r][act[r]] -
+ *   returns[r]; loss[k] = mean(td_k^2 * weight) (weight NULL: 1); grad_k[b, num_actions] is
+ *   written in full, 2 td_k weight / b at the taken action and zero elsewhere; td_out[r] =
+ *   fl(fl(td_1 + td_2) / 2), torch's f32 expression bit for bit; total (may be NULL) receives the
+ *   sum of the losses.  An action outside [0, num_actions) gives a NaN td_out and loss and an
+ *   all-zero gradient row.
+ * tsrl_dsac_actor_loss_fwd_bwd: the actor and temperature losses (:127-144); q1, q2 are the
+ *   critics' outputs, no gradient goes to them.  loss[0] = -mean(alpha H + V); g_logits[r][j] =
+ *   -(1 / b) p_j [(qm_j - V) - alpha (lp_j + H)], the derivative through softmax and entropy.
+ *   With log_alpha: loss[1] = -log_alpha mean(target_entropy - H), g_log_alpha[0] =
+ *   -mean(target_entropy - H); log_alpha NULL leaves loss[1] and g_log_alpha untouched
+ *   (g_log_alpha may then be NULL).
+ * Both losses: every batch sum is f64 in a fixed order (lanes, waves, workgroups), bit-identical
+ *   between runs.  partials: 2 * tsrl_ddpg_num_partials(b) doubles, read and written only when
+ *   that count is > 1 (b > 256: a second one-lane launch folds them), else may be NULL.
+ * ------------------------------------------------------------------------------- */
+int tsrl_dsac_target(const float* logits, const float* q1, const float* q2, const float* alpha,
+                     int64_t b, int64_t num_actions, float* out, void* stream);
+int tsrl_dsac_q_loss_fwd_bwd(const float* q1, const float* q2, const int64_t* act,
+                             const float* returns, const float* weight, int64_t b,
+                             int64_t num_actions, float* grad1, float* grad2, float* td_out,
+                             double* partials, float* loss, float* total, void* stream);
+int tsrl_dsac_actor_loss_fwd_bwd(const float* logits, const float* q1, const float* q2,
+                                 const float* alpha, const float* log_alpha,
+                                 double target_entropy, int64_t b, int64_t num_actions,
+                                 float* g_logits, double* partials, float* loss,
+                                 float* g_log_alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,11 @@ _SIGS = {
     "tsrl_sac_target": ([_p, _p, _p, _p, _i64, _p, _p], ctypes.c_int),
     "tsrl_sac_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _d, _i64, _p, _p, _p, _p, _p, _p, _p],
                                     ctypes.c_int),
+    "tsrl_dsac_target": ([_p, _p, _p, _p, _i64, _i64, _p, _p], ctypes.c_int),
+    "tsrl_dsac_q_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
+                                 ctypes.c_int),
+    "tsrl_dsac_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p],
+                                     ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

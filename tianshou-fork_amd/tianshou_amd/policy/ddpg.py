@@ -17,10 +17,10 @@ What stays on torch: a network with module buffers or another optimiser (``soft_
 ``optim.step()`` for that network; no graph replay), and ``fused = False`` -- the reference's
 op sequence on the GPU, kept as the comparison leg of tools/ddpg_update_bench.py.
 
-SACPolicy (policy/sac.py) builds on the same hooks.  Not built: REDQ, an OffpolicyTrainer,
-data-parallel updates, a fused act kernel for deterministic actors (the Collector keeps such a
-policy on its eager device step) and reward normalisation (compute_nstep_return asserts
-against it).
+SACPolicy (policy/sac.py) and DiscreteSACPolicy (policy/discrete_sac.py) build on the same
+hooks.  Not built: REDQ, an OffpolicyTrainer, data-parallel updates, a fused act kernel for
+deterministic actors (the Collector keeps such a policy on its eager device step) and reward
+normalisation (compute_nstep_return asserts against it).
 """
 import warnings
 from copy import deepcopy
@@ -393,6 +393,12 @@ class DDPGPolicy(BasePolicy):
         captured graph, handed to _step after its other arguments.  None here."""
         return ()
 
+    def _learn_act(self, batch: Batch, dev, n: int) -> torch.Tensor:
+        """``batch.act`` as the fused update takes it: f32 [n, act_dim] here; the int64 [n]
+        indices of DiscreteSACPolicy."""
+        return torch.as_tensor(batch.act, device=dev).to(torch.float32).reshape(n, -1) \
+            .contiguous()
+
     def _learn_torch(self, batch: Batch, do_actor: bool):
         """The reference's op sequence as written (ddpg.py:184-194, td3.py:111-128), on
         whatever device the networks live on; returns (losses, per-row vector)."""
@@ -427,8 +433,7 @@ class DDPGPolicy(BasePolicy):
             n = len(batch.returns)
             weight = batch.get("weight", None)
             obs = batch.obs
-            act = torch.as_tensor(batch.act, device=dev).to(torch.float32).reshape(n, -1) \
-                .contiguous()
+            act = self._learn_act(batch, dev, n)
             returns = _f32_rows(batch.returns, dev, n)
             w = None if weight is None else _f32_rows(weight, dev, n)
             draws = self._learn_draws(act)

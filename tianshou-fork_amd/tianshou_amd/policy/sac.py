@@ -19,6 +19,9 @@ Differences from the reference: on the fused path ``dist`` is built with
 ``validate_args=False`` (no launch and no host sync for the argument check; the torch leg
 validates as the reference does), and ``batch.weight`` and the actions are f32 device tensors.
 ``fused = False`` is the reference's op sequence, the comparison leg and the CPU path.
+
+DiscreteSACPolicy (policy/discrete_sac.py) subclasses this class.  Not built: REDQ, an
+OffpolicyTrainer and data-parallel updates.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union

@@ -1,15 +1,19 @@
-"""Time DDPGPolicy.update(), TD3Policy.update() and SACPolicy.update() (sample + process_fn +
-learn + post_process_fn) on one filled VectorReplayBuffer: HIP events around each of --updates
-updates after --warmup.
+"""Time DDPGPolicy.update(), TD3Policy.update(), SACPolicy.update() and
+DiscreteSACPolicy.update() (sample + process_fn + learn + post_process_fn) on one filled
+VectorReplayBuffer: HIP events around each of --updates updates after --warmup.
 
     python tools/ddpg_update_bench.py              # DDPG and TD3, both shapes, three legs
     python tools/ddpg_update_bench.py --policies sac
+    python tools/ddpg_update_bench.py --policies dsac --configs c12,a128 --torch-runs 1
 
 Shapes: "d17" obs 17 / act 6 (examples/mujoco/mujoco_td3.py on HalfCheetah) and "d376" obs 376 /
 act 17 (Humanoid), hidden (256, 256), batch 256, Adam, n_step 1; TD3 with its default
 update_actor_freq 2, so its mean covers both step kinds; SAC (examples/mujoco/mujoco_sac.py)
 with ActorProb(unbounded, conditioned_sigma) and the automatic temperature (target_entropy =
--act, Adam on log_alpha).
+-act, Adam on log_alpha).  DiscreteSAC (examples/atari/atari_sac.py's heads without the conv
+trunk): "c12" obs 12 -> (128, 128, 128) -> 6 actions at batch 64 and "a128" obs 128 -> (256,
+256) -> 18 actions at batch 256, DiscreteActor(softmax_output=False) and two DiscreteCritic
+nets, automatic temperature (target_entropy = 0.98 log A).
 Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), "eager"
 (graph_learn=False: the fused kernels and the flat Adam passes launched eagerly) and "torch"
 (fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
@@ -37,13 +41,17 @@ ap.add_argument("--torch-runs", type=int, default=3)
 args = ap.parse_args()
 
 from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
-from tianshou_amd.policy import DDPGPolicy, SACPolicy, TD3Policy  # noqa: E402
-from tianshou_amd.utils.net import Actor, ActorProb, Critic, Net  # noqa: E402
+from tianshou_amd.policy import (DDPGPolicy, DiscreteSACPolicy, SACPolicy,  # noqa: E402
+                                 TD3Policy)
+from tianshou_amd.utils.net import (Actor, ActorProb, Critic, DiscreteActor,  # noqa: E402
+                                    DiscreteCritic, Net)
 
 dev = torch.device("cuda", 0)
 CONFIGS = {
     "d17": dict(E=8, T=512, D=17, A=6, batch=256),
     "d376": dict(E=8, T=512, D=376, A=17, batch=256),
+    "c12": dict(E=8, T=512, D=12, A=6, batch=64, hidden=(128, 128, 128), discrete=True),
+    "a128": dict(E=8, T=512, D=128, A=18, batch=256, discrete=True),
 }
 HIDDEN = (256, 256)
 LEGS = {"graph": dict(graph_learn=True), "eager": dict(graph_learn=False),
@@ -60,9 +68,10 @@ def fill(cfg):
         nxt = rng.standard_normal((E, D)).astype(np.float32)
         done = rng.random(E) < 0.02
         term = done & (rng.random(E) < 0.5)
-        buf.add(Batch(obs=obs, act=rng.uniform(-1, 1, (E, A)).astype(np.float32),
-                      rew=rng.standard_normal(E), terminated=term, truncated=done & ~term,
-                      obs_next=nxt), buffer_ids=np.arange(E))
+        act = rng.integers(0, A, E).astype(np.int64) if cfg.get("discrete") else \
+            rng.uniform(-1, 1, (E, A)).astype(np.float32)
+        buf.add(Batch(obs=obs, act=act, rew=rng.standard_normal(E), terminated=term,
+                      truncated=done & ~term, obs_next=nxt), buffer_ids=np.arange(E))
         obs = nxt
     return buf
 
@@ -70,6 +79,8 @@ def fill(cfg):
 def make_policy(kind, cfg, leg):
     torch.manual_seed(0)
     D, A = cfg["D"], cfg["A"]
+    if kind == "dsac":
+        return make_dsac(cfg, leg)
     if kind == "sac":
         actor = ActorProb(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev,
                           unbounded=True, conditioned_sigma=True).to(dev)
@@ -96,9 +107,28 @@ def make_policy(kind, cfg, leg):
     return policy
 
 
+def make_dsac(cfg, leg):
+    D, A, hidden = cfg["D"], cfg["A"], cfg.get("hidden", HIDDEN)
+    actor = DiscreteActor(Net(D, hidden_sizes=hidden, device=dev), (A,), softmax_output=False,
+                          device=dev).to(dev)
+    critics = [DiscreteCritic(Net(D, hidden_sizes=hidden, device=dev), last_size=A,
+                              device=dev).to(dev) for _ in range(2)]
+    a_opt = torch.optim.Adam(actor.parameters(), lr=3e-4)
+    c_opt = [torch.optim.Adam(c.parameters(), lr=3e-4) for c in critics]
+    log_alpha = torch.zeros(1, requires_grad=True, device=dev)
+    alpha = (0.98 * float(np.log(A)), log_alpha, torch.optim.Adam([log_alpha], lr=3e-4))
+    policy = DiscreteSACPolicy(actor, a_opt, critics[0], c_opt[0], critics[1], c_opt[1],
+                               tau=0.005, gamma=0.99, alpha=alpha, estimation_step=1).to(dev)
+    for k, v in LEGS[leg].items():
+        setattr(policy, k, v)
+    return policy
+
+
 for kind in args.policies.split(","):
     for name in args.configs.split(","):
         cfg = CONFIGS[name]
+        if bool(cfg.get("discrete")) != (kind == "dsac"):
+            raise SystemExit(f"config {name} does not fit policy {kind}")
         buf = fill(cfg)
         for leg in args.legs.split(","):
             for run in range(args.torch_runs if leg == "torch" else 1):
