@@ -601,6 +601,10 @@ int tsrl_cat_gumbel_argmax(const float* logits, const float* u, int64_t n, int64
  *   2-3 like live rows and enter the weight gradients with a zero loss gradient (a product,
  *   not a select), so a NaN or Inf there would reach every layer-2/3 gradient.  They get
  *   zero weight: no output depends on their (finite) values.
+ *   tsrl_ppo_eval has NO such requirement: it is forward only, every row's outputs come from
+ *   that row's own fragment columns, and rows n.. of the last 32-row tile are never stored, so
+ *   they may hold anything (NaN and Inf included) without changing a bit of the outputs of the
+ *   rows < n.  tests/test_gpu_mlp_eval.py holds this.
  * tsrl_mlp_dw: first-layer gradients dW = dZ1^T X[idx], db = column sums of dZ1.  Row
  *   indices idx[] and the pitch ldx must be < 2^32 (the row offsets are 32 x 32-bit
  *   products; ldx is checked).
@@ -650,8 +654,13 @@ int tsrl_ppo_tail_stage(const float* h1frag, int64_t n, const int64_t* idx,
                         float* grad_log_std, int stages, void* stream);
 /* tsrl_ppo_eval: forward only (process_fn): value_out[n] = critic(obs) and, when logp_out is
  * given, logp_out[n] = log N(act | mu(obs), exp(log_std)) summed over the action dims, from
- * the fragment-layout layer-1 activations of tsrl_mlp_l1_fwd (critic only: the actor tiles
- * are not read). */
+ * the fragment-layout layer-1 activations of tsrl_mlp_l1_fwd.
+ * Values only (logp_out NULL; act is then ignored and may be NULL): the critic's half alone
+ * runs.  The actor's pointers of *w (w2a, b2a, w3a, b3a, log_std) may be NULL and the actor's
+ * feature tiles of h1frag are not read, and value_out has the same bits as in a call with
+ * logp_out.  With logp_out every pointer of *w and act are required; the critic's four
+ * pointers always are (a NULL one is an argument error, nothing is launched).  The same holds
+ * for tsrl_ppo_eval_fused.  n == 0 returns 0 and writes nothing. */
 int tsrl_ppo_eval(const float* h1frag, int64_t n, const tsrl_tail_weights* w, int64_t act_dim,
                   const float* act, float* value_out, float* logp_out, void* stream);
 

@@ -1,6 +1,7 @@
-"""Shared by tests/test_gpu_mlp.py and tests/test_gpu_mlp_bwd.py: the fragment-layout reader,
-the perturbed get_actor_critic networks and the torch restatement of one PPO minibatch
-(ppo.py:121-142), whole (from the observations) or from the heads' outputs only."""
+"""Shared by tests/test_gpu_mlp.py, tests/test_gpu_mlp_bwd.py and tests/test_gpu_mlp_eval.py:
+the fragment-layout reader and writer (the latter checked on the host by
+tests/test_mlp_layout.py), the perturbed get_actor_critic networks and the torch restatement
+of one PPO minibatch (ppo.py:121-142), whole (from the observations) or from the heads' outputs only."""
 import torch
 from torch.distributions import Independent, Normal
 
@@ -24,6 +25,30 @@ def frag_to_rows(frag, n, nt=4):
             out[(torch.arange(ntile)[:, None] * 32 + rows[None, :]).reshape(-1),
                 (32 * ft + feat).repeat(ntile)] = f[:, ft, :, r].reshape(-1)
     return out[:n]
+
+
+def frag_floats(n):
+    """tsrl_mlp_frag_floats restated for the CPU (csrc/mlp.hip): whole 128-row blocks of 128
+    features."""
+    return (n + 127) // 128 * 128 * 128
+
+
+def rows_to_frag(R, fill=0.0):
+    """The inverse of frag_to_rows: [n, 128] -> the frag_floats(n) floats of the x6.h frag_off4
+    layout ([row tile][feature tile][q][lane][4]) on R's device; every float of the pad rows
+    n.. of the last 128-row block holds fill."""
+    n = R.shape[0]
+    assert R.dim() == 2 and R.shape[1] == 128 and n > 0
+    ntile = frag_floats(n) // (4 * 1024)
+    full = torch.full((ntile * 32, 128), fill, dtype=R.dtype, device=R.device)
+    full[:n] = R
+    lane = torch.arange(64, device=R.device)
+    r = torch.arange(16, device=R.device)
+    feat = _rho(r)[None, :] + 4 * (lane >> 5)[:, None]          # [64, 16]
+    rows = (lane & 31)[:, None].expand(64, 16)
+    # [row tile][feature tile][lane][r = 4 q + e] -> [row tile][feature tile][q][lane][e]
+    g = full.view(ntile, 32, 4, 32).permute(0, 2, 1, 3)[:, :, rows, feat]
+    return g.view(ntile, 4, 64, 4, 4).permute(0, 1, 3, 2, 4).contiguous().view(-1)
 
 
 def _nets(D, A, dev, seed):

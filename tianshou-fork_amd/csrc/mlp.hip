@@ -1329,6 +1329,9 @@ extern "C" int tsrl_ppo_eval(const float* h1frag, int64_t n, const tsrl_tail_wei
     if (n == 0) return 0;
     TSRL_CHECK_ARG(h1frag && wt && value_out && (!logp_out || act),
                    "tsrl_ppo_eval: null pointer");
+    TSRL_CHECK_ARG(wt->w2c && wt->b2c && wt->w3c && wt->b3c &&
+                       (!logp_out || (wt->w2a && wt->b2a && wt->w3a && wt->b3a && wt->log_std)),
+                   "tsrl_ppo_eval: null weight");
     TSRL_CHECK_ARG(aligned16(h1frag), "tsrl_ppo_eval: h1frag not 16-byte aligned");
     TailWeights w{wt->w2a, wt->b2a, wt->w2c, wt->b2c, wt->w3a, wt->b3a, wt->w3c, wt->b3c,
                   wt->log_std};
