@@ -965,6 +965,42 @@ int tsrl_dsac_actor_loss_fwd_bwd(const float* logits, const float* q1, const flo
                                  float* g_logits, double* partials, float* loss,
                                  float* g_log_alpha, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * REDQPolicy (tianshou/policy/modelfree/redq.py), csrc/redq.hip.  q, qs and gq are row-major
+ * [E, b] f32, the critic ensemble's [E, b, 1] output: any ensemble size E >= 1 and batch b >= 1,
+ * both runtime arguments.  One lane owns a column and walks the E members.  alpha and log_alpha
+ * are pointers to one device f32 each, read by the kernel.  The reparameterised sample is
+ * tsrl_sac_sample_fwd / _bwd.
+ * tsrl_redq_target: _target_q (redq.py:150-155): out[i] = fl(r[i] - fl(alpha * log_prob[i])), r
+ *   the min (mode 0; a NaN handed through as torch.min hands it through) or the mean (mode 1;
+ *   summed in f64 in subset order, rounded once) of qs[idx[m], i] over the M drawn members.  idx
+ *   is the draw as int32 on the device, idx_host the same M values on the host: the call
+ *   validates them there and fails, launching nothing, when one is outside [0, E) or when M < 1
+ *   or M > E.
+ * tsrl_redq_q_loss_fwd_bwd: redq.py:161-169.  td[e, i] = q[e, i] - returns[i]; loss[0] = the mean
+ *   over all E b elements of fl(fl(td^2) * weight[i]) (weight NULL: 1); gq[e, i] = 2 td weight /
+ *   (E b); td_mean[i] = mean_e td[e, i], summed in f64.  With E = 1 loss and gq are
+ *   tsrl_q_mse_fwd_bwd's of one critic.  partials: tsrl_ddpg_num_partials(b) doubles.
+ * tsrl_redq_actor_loss_fwd_bwd: redq.py:176-189.  loss[0] = mean_i(fl(alpha * log_prob[i]) -
+ *   mean_e q[e, i]); gq[e, i] = -1 / (E b); g_logp[i] = fl(alpha * (1 / b)).  With log_alpha:
+ *   loss[1] = -log_alpha mean(log_prob + target_entropy) and g_log_alpha[0] = -mean(fl(log_prob
+ *   + (float)target_entropy)); log_alpha NULL leaves loss[1] and g_log_alpha untouched
+ *   (g_log_alpha may then be NULL).  partials: 2 * tsrl_ddpg_num_partials(b) doubles.
+ * Both losses: every batch sum is f64 in the fixed order of tsrl_q_mse_fwd_bwd; partials are read
+ *   and written only when their count is > 1 (b > 256: a second one-lane launch folds them),
+ *   else may be NULL.
+ * ------------------------------------------------------------------------------- */
+int tsrl_redq_target(const float* qs, int64_t E, int64_t b, const int32_t* idx,
+                     const int32_t* idx_host, int64_t M, int mode, const float* log_prob,
+                     const float* alpha, float* out, void* stream);
+int tsrl_redq_q_loss_fwd_bwd(const float* q, const float* returns, const float* weight,
+                             int64_t E, int64_t b, float* gq, float* td_mean, double* partials,
+                             float* loss, void* stream);
+int tsrl_redq_actor_loss_fwd_bwd(const float* q, const float* log_prob, const float* alpha,
+                                 const float* log_alpha, double target_entropy, int64_t E,
+                                 int64_t b, float* gq, float* g_logp, double* partials,
+                                 float* loss, float* g_log_alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

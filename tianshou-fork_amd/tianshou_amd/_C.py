@@ -236,6 +236,10 @@ _SIGS = {
                                  ctypes.c_int),
     "tsrl_dsac_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p],
                                      ctypes.c_int),
+    "tsrl_redq_target": ([_p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_redq_q_loss_fwd_bwd": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_redq_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p, _p],
+                                     ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

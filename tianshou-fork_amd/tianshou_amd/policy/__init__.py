@@ -11,7 +11,8 @@ from tianshou_amd.policy.ddpg import DDPGPolicy
 from tianshou_amd.policy.td3 import TD3Policy
 from tianshou_amd.policy.sac import SACPolicy
 from tianshou_amd.policy.discrete_sac import DiscreteSACPolicy
+from tianshou_amd.policy.redq import REDQPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
            "DQNPolicy", "C51Policy", "QRDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy",
-           "DiscreteSACPolicy"]
+           "DiscreteSACPolicy", "REDQPolicy"]

@@ -17,10 +17,10 @@ What stays on torch: a network with module buffers or another optimiser (``soft_
 ``optim.step()`` for that network; no graph replay), and ``fused = False`` -- the reference's
 op sequence on the GPU, kept as the comparison leg of tools/ddpg_update_bench.py.
 
-SACPolicy (policy/sac.py) and DiscreteSACPolicy (policy/discrete_sac.py) build on the same
-hooks.  Not built: REDQ, an OffpolicyTrainer, data-parallel updates, a fused act kernel for
-deterministic actors (the Collector keeps such a policy on its eager device step) and reward
-normalisation (compute_nstep_return asserts against it).
+SACPolicy (policy/sac.py), DiscreteSACPolicy (policy/discrete_sac.py) and REDQPolicy
+(policy/redq.py) build on the same hooks.  Not built: an OffpolicyTrainer, data-parallel
+updates, a fused act kernel for deterministic actors (the Collector keeps such a policy on its
+eager device step) and reward normalisation (compute_nstep_return asserts against it).
 """
 import warnings
 from copy import deepcopy

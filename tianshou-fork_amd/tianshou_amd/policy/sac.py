@@ -20,8 +20,9 @@ Differences from the reference: on the fused path ``dist`` is built with
 validates as the reference does), and ``batch.weight`` and the actions are f32 device tensors.
 ``fused = False`` is the reference's op sequence, the comparison leg and the CPU path.
 
-DiscreteSACPolicy (policy/discrete_sac.py) subclasses this class.  Not built: REDQ, an
-OffpolicyTrainer and data-parallel updates.
+DiscreteSACPolicy (policy/discrete_sac.py) subclasses this class; REDQPolicy (policy/redq.py)
+shares _SquashedGaussianMixin with it.  Not built: an OffpolicyTrainer and data-parallel
+updates.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -159,33 +160,13 @@ def sac_actor_loss(q1: torch.Tensor, q2: torch.Tensor, log_prob: torch.Tensor,
     return handle, loss, g_la
 
 
-class SACPolicy(DDPGPolicy):
-    """Constructor arguments, defaults and assertions as the reference's (sac.py:54-94); the
-    device-path attributes are DDPGPolicy's."""
+class _SquashedGaussianMixin:
+    """What SACPolicy and REDQPolicy (policy/redq.py) share on top of DDPGPolicy: the
+    tanh-squashed Gaussian ``forward``, the N(0, 1) draws, the temperature as a device tensor and
+    its one-parameter flat optimiser, and the graph keys that follow from them."""
 
-    _critic_names = ("critic1", "critic2")
-    _sync_order = ("critic1", "critic2")  # sac.py:103-105: the actor has no target copy
-    _optim_order = ("critic1", "critic2", "actor")
-    # the Collector keeps this policy on its eager device step: every forward draws
-    eager_collect_step = True
-
-    def __init__(self, actor: torch.nn.Module, actor_optim: torch.optim.Optimizer,
-                 critic1: torch.nn.Module, critic1_optim: torch.optim.Optimizer,
-                 critic2: torch.nn.Module, critic2_optim: torch.optim.Optimizer,
-                 tau: float = 0.005, gamma: float = 0.99,
-                 alpha: Union[float, Tuple[float, torch.Tensor, torch.optim.Optimizer]] = 0.2,
-                 reward_normalization: bool = False, estimation_step: int = 1,
-                 exploration_noise: Optional[BaseNoise] = None,
-                 deterministic_eval: bool = True, **kwargs: Any) -> None:
-        super().__init__(None, None, None, None, tau, gamma, exploration_noise,
-                         reward_normalization, estimation_step, **kwargs)
-        self.actor, self.actor_optim = actor, actor_optim
-        self.critic1, self.critic1_old = critic1, deepcopy(critic1)
-        self.critic1_old.eval()
-        self.critic1_optim = critic1_optim
-        self.critic2, self.critic2_old = critic2, deepcopy(critic2)
-        self.critic2_old.eval()
-        self.critic2_optim = critic2_optim
+    def _init_temperature(self, alpha, deterministic_eval: bool) -> None:
+        """sac.py:83-94 / redq.py:87-104."""
         self._is_auto_alpha = False
         self._alpha: Union[float, torch.Tensor]
         if isinstance(alpha, tuple):
@@ -241,6 +222,92 @@ class SACPolicy(DDPGPolicy):
             log_prob = log_prob - torch.log((1 - act.pow(2)) + EPS32).sum(-1, keepdim=True)
         return Batch(logits=logits, act=act, state=hidden, dist=dist, log_prob=log_prob)
 
+    def _bind_alpha(self) -> Optional[FlatAdam]:
+        """The one-parameter flat storage of ``log_alpha`` when ``alpha_optim`` is a plain
+        Adam / RMSprop over it (None: torch's step, and no graph)."""
+        if not (self._is_auto_alpha and self.fused and self.fused_adam
+                and self._log_alpha.is_cuda and self._log_alpha.dtype == torch.float32):
+            return None
+        if self._alpha_fa is None:
+            self._alpha_fa = FlatAdam([self._log_alpha])
+        fa = self._alpha_fa
+        if not fa.bind_adam(self._alpha_optim):
+            return None
+        fa.bind_grads()
+        fa.set_lr()
+        return fa
+
+    def learn(self, batch: Batch, **kwargs: Any) -> Dict[str, float]:
+        """sac.py:147-190 / redq.py:159-200; see DDPGPolicy.learn."""
+        self._bind_alpha()
+        return super().learn(batch, **kwargs)
+
+    def _learn_draws(self, act: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        if not self._draws():
+            return ()
+        return (_rows(self._rsample_noise(act.shape, act.device)),)
+
+    def _alpha_flat(self) -> Optional[FlatAdam]:
+        """log_alpha's flat storage while it serves ``alpha_optim``, else None."""
+        fa = self._alpha_fa
+        return fa if fa is not None and fa.adam_bound(self._alpha_optim) else None
+
+    def _graph_ok(self, obs, n: int) -> bool:
+        if self._is_auto_alpha and self._alpha_flat() is None:
+            return False
+        return super()._graph_ok(obs, n)
+
+    def _graph_addr(self, fas) -> tuple:
+        addr = super()._graph_addr(fas)
+        dev = next(self.actor.parameters()).device
+        extra = [self._alpha_tensor(dev).data_ptr()]
+        if self._is_auto_alpha:
+            extra += [self._log_alpha.data_ptr(), self._alpha_fa.flat_grad.data_ptr()]
+        return addr + (tuple(extra),)
+
+    def _alpha_step(self, g_la: torch.Tensor, alpha: torch.Tensor) -> None:
+        """The temperature's optimiser pass on the loss kernel's gradient ``g_la`` and alpha =
+        exp(log_alpha) in place (sac.py:174-177)."""
+        fa = self._alpha_flat()
+        if fa is not None:  # the gradient landed in log_alpha's flat .grad
+            fa.clip_adam(None)
+            torch.exp(self._log_alpha.detach(), out=alpha)
+        else:  # another optimiser: torch's step on the kernel's gradient
+            self._alpha_optim.zero_grad()
+            self._log_alpha.grad = g_la.to(self._log_alpha.dtype).view_as(self._log_alpha)
+            self._alpha_optim.step()
+            alpha.copy_(self._log_alpha.detach().exp())
+
+
+class SACPolicy(_SquashedGaussianMixin, DDPGPolicy):
+    """Constructor arguments, defaults and assertions as the reference's (sac.py:54-94); the
+    device-path attributes are DDPGPolicy's."""
+
+    _critic_names = ("critic1", "critic2")
+    _sync_order = ("critic1", "critic2")  # sac.py:103-105: the actor has no target copy
+    _optim_order = ("critic1", "critic2", "actor")
+    # the Collector keeps this policy on its eager device step: every forward draws
+    eager_collect_step = True
+
+    def __init__(self, actor: torch.nn.Module, actor_optim: torch.optim.Optimizer,
+                 critic1: torch.nn.Module, critic1_optim: torch.optim.Optimizer,
+                 critic2: torch.nn.Module, critic2_optim: torch.optim.Optimizer,
+                 tau: float = 0.005, gamma: float = 0.99,
+                 alpha: Union[float, Tuple[float, torch.Tensor, torch.optim.Optimizer]] = 0.2,
+                 reward_normalization: bool = False, estimation_step: int = 1,
+                 exploration_noise: Optional[BaseNoise] = None,
+                 deterministic_eval: bool = True, **kwargs: Any) -> None:
+        super().__init__(None, None, None, None, tau, gamma, exploration_noise,
+                         reward_normalization, estimation_step, **kwargs)
+        self.actor, self.actor_optim = actor, actor_optim
+        self.critic1, self.critic1_old = critic1, deepcopy(critic1)
+        self.critic1_old.eval()
+        self.critic1_optim = critic1_optim
+        self.critic2, self.critic2_old = critic2, deepcopy(critic2)
+        self.critic2_old.eval()
+        self.critic2_optim = critic2_optim
+        self._init_temperature(alpha, deterministic_eval)
+
     # -- process_fn -----------------------------------------------------------------------------
     def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
         """sac.py:137-145: min over the target critics at the sampled next action, less
@@ -290,49 +357,6 @@ class SACPolicy(DDPGPolicy):
         self.sync_weight()
         return torch.stack([t.to(torch.float32) for t in losses]), td
 
-    def _bind_alpha(self) -> Optional[FlatAdam]:
-        """The one-parameter flat storage of ``log_alpha`` when ``alpha_optim`` is a plain
-        Adam / RMSprop over it (None: torch's step, and no graph)."""
-        if not (self._is_auto_alpha and self.fused and self.fused_adam
-                and self._log_alpha.is_cuda and self._log_alpha.dtype == torch.float32):
-            return None
-        if self._alpha_fa is None:
-            self._alpha_fa = FlatAdam([self._log_alpha])
-        fa = self._alpha_fa
-        if not fa.bind_adam(self._alpha_optim):
-            return None
-        fa.bind_grads()
-        fa.set_lr()
-        return fa
-
-    def learn(self, batch: Batch, **kwargs: Any) -> Dict[str, float]:
-        """sac.py:147-190; see DDPGPolicy.learn."""
-        self._bind_alpha()
-        return super().learn(batch, **kwargs)
-
-    def _learn_draws(self, act: torch.Tensor) -> Tuple[torch.Tensor, ...]:
-        if not self._draws():
-            return ()
-        return (_rows(self._rsample_noise(act.shape, act.device)),)
-
-    def _alpha_flat(self) -> Optional[FlatAdam]:
-        """log_alpha's flat storage while it serves ``alpha_optim``, else None."""
-        fa = self._alpha_fa
-        return fa if fa is not None and fa.adam_bound(self._alpha_optim) else None
-
-    def _graph_ok(self, obs, n: int) -> bool:
-        if self._is_auto_alpha and self._alpha_flat() is None:
-            return False
-        return super()._graph_ok(obs, n)
-
-    def _graph_addr(self, fas) -> tuple:
-        addr = super()._graph_addr(fas)
-        dev = next(self.actor.parameters()).device
-        extra = [self._alpha_tensor(dev).data_ptr()]
-        if self._is_auto_alpha:
-            extra += [self._log_alpha.data_ptr(), self._alpha_fa.flat_grad.data_ptr()]
-        return addr + (tuple(extra),)
-
     def _step(self, fas, obs, act, returns, weight, do_actor: bool, td_out: torch.Tensor,
               loss_out: torch.Tensor, eps: Optional[torch.Tensor] = None) -> None:
         """One update (sac.py:147-179): both critics' forward, their fused losses, backward
@@ -359,13 +383,6 @@ class SACPolicy(DDPGPolicy):
             q1a, q2a, log_prob, alpha, self._log_alpha, self._target_entropy, loss_out[2:4],
             None if fa is None else fa.flat_grad)  # the gradient lands in log_alpha's .grad
         self._backward_step(handle, ("actor",), fas)
-        if fa is not None:
-            fa.clip_adam(None)
-            torch.exp(self._log_alpha.detach(), out=alpha)
-        else:  # another optimiser: torch's step on the kernel's gradient
-            self._alpha_optim.zero_grad()
-            self._log_alpha.grad = g_la.to(self._log_alpha.dtype).view_as(self._log_alpha)
-            self._alpha_optim.step()
-            alpha.copy_(self._log_alpha.detach().exp())
+        self._alpha_step(g_la, alpha)
         loss_out[4:5].copy_(alpha)
         self.sync_weight()

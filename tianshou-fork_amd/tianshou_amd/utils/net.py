@@ -87,6 +87,32 @@ class Linear(nn.Linear):
         return _LinearFn.apply(x, self.weight, self.bias)
 
 
+class EnsembleLinear(nn.Module):
+    """The linear layer of an ensemble of networks (common.py:402-432): ``weight`` [E, in, out]
+    and ``bias`` [E, 1, out], initialised by the reference's two ``torch.rand`` calls, so a
+    seeded construction and a state_dict equal the reference's.  ``x`` is [b, in] (every member
+    sees the same rows) or [E, b, in]; the output is [E, b, out], one batched GEMM."""
+
+    def __init__(self, ensemble_size: int, in_feature: int, out_feature: int,
+                 bias: bool = True) -> None:
+        super().__init__()
+        k = np.sqrt(1.0 / in_feature)  # PyTorch's default initialiser
+        weight_data = torch.rand((ensemble_size, in_feature, out_feature)) * 2 * k - k
+        self.weight = nn.Parameter(weight_data, requires_grad=True)
+        self.bias: Optional[nn.Parameter]
+        if bias:
+            bias_data = torch.rand((ensemble_size, 1, out_feature)) * 2 * k - k
+            self.bias = nn.Parameter(bias_data, requires_grad=True)
+        else:
+            self.bias = None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = torch.matmul(x, self.weight)
+        if self.bias is not None:
+            x = x + self.bias
+        return x
+
+
 def miniblock(input_size, output_size=0, norm_layer=None, activation=None,
               linear_layer: Type[nn.Linear] = Linear):
     layers = [linear_layer(input_size, output_size)]

@@ -1,10 +1,11 @@
-"""Time DDPGPolicy.update(), TD3Policy.update(), SACPolicy.update() and
-DiscreteSACPolicy.update() (sample + process_fn + learn + post_process_fn) on one filled
+"""Time DDPGPolicy.update(), TD3Policy.update(), SACPolicy.update(), DiscreteSACPolicy.update()
+and REDQPolicy.update() (sample + process_fn + learn + post_process_fn) on one filled
 VectorReplayBuffer: HIP events around each of --updates updates after --warmup.
 
     python tools/ddpg_update_bench.py              # DDPG and TD3, both shapes, three legs
     python tools/ddpg_update_bench.py --policies sac
     python tools/ddpg_update_bench.py --policies dsac --configs c12,a128 --torch-runs 1
+    python tools/ddpg_update_bench.py --policies redq --updates 200 --warmup 10
 
 Shapes: "d17" obs 17 / act 6 (examples/mujoco/mujoco_td3.py on HalfCheetah) and "d376" obs 376 /
 act 17 (Humanoid), hidden (256, 256), batch 256, Adam, n_step 1; TD3 with its default
@@ -13,7 +14,12 @@ with ActorProb(unbounded, conditioned_sigma) and the automatic temperature (targ
 -act, Adam on log_alpha).  DiscreteSAC (examples/atari/atari_sac.py's heads without the conv
 trunk): "c12" obs 12 -> (128, 128, 128) -> 6 actions at batch 64 and "a128" obs 128 -> (256,
 256) -> 18 actions at batch 256, DiscreteActor(softmax_output=False) and two DiscreteCritic
-nets, automatic temperature (target_entropy = 0.98 log A).
+nets, automatic temperature (target_entropy = 0.98 log A).  REDQ (examples/mujoco/
+mujoco_redq.py): a 10-member EnsembleLinear critic, subset 2, the actor and temperature of the
+SAC leg.  Its two step kinds are timed apart ("critic_ms_*": the update that steps the ensemble
+alone, "actor_ms_*": the one that steps actor and temperature too), with --redq-actor-delay 2
+so that they alternate and each gets half of --updates; what a kind costs does not depend on the
+delay.  "update_ms_at_delay_20" weighs their means 19 : 1, the example's actor_delay.
 Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), "eager"
 (graph_learn=False: the fused kernels and the flat Adam passes launched eagerly) and "torch"
 (fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
@@ -38,13 +44,14 @@ ap.add_argument("--legs", default="graph,eager,torch")
 ap.add_argument("--updates", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--torch-runs", type=int, default=3)
+ap.add_argument("--redq-actor-delay", type=int, default=2)
 args = ap.parse_args()
 
 from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
-from tianshou_amd.policy import (DDPGPolicy, DiscreteSACPolicy, SACPolicy,  # noqa: E402
-                                 TD3Policy)
+from tianshou_amd.policy import (DDPGPolicy, DiscreteSACPolicy, REDQPolicy,  # noqa: E402
+                                 SACPolicy, TD3Policy)
 from tianshou_amd.utils.net import (Actor, ActorProb, Critic, DiscreteActor,  # noqa: E402
-                                    DiscreteCritic, Net)
+                                    DiscreteCritic, EnsembleLinear, Net)
 
 dev = torch.device("cuda", 0)
 CONFIGS = {
@@ -54,6 +61,7 @@ CONFIGS = {
     "a128": dict(E=8, T=512, D=128, A=18, batch=256, discrete=True),
 }
 HIDDEN = (256, 256)
+REDQ_ENSEMBLE, REDQ_SUBSET = 10, 2
 LEGS = {"graph": dict(graph_learn=True), "eager": dict(graph_learn=False),
         "torch": dict(fused=False)}
 
@@ -81,6 +89,8 @@ def make_policy(kind, cfg, leg):
     D, A = cfg["D"], cfg["A"]
     if kind == "dsac":
         return make_dsac(cfg, leg)
+    if kind == "redq":
+        return make_redq(cfg, leg)
     if kind == "sac":
         actor = ActorProb(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev,
                           unbounded=True, conditioned_sigma=True).to(dev)
@@ -124,6 +134,37 @@ def make_dsac(cfg, leg):
     return policy
 
 
+def make_redq(cfg, leg):
+    D, A = cfg["D"], cfg["A"]
+    actor = ActorProb(Net(D, hidden_sizes=HIDDEN, device=dev), (A,), device=dev,
+                      unbounded=True, conditioned_sigma=True).to(dev)
+
+    def linear(x, y):
+        return EnsembleLinear(REDQ_ENSEMBLE, x, y)
+
+    critics = Critic(Net(D, A, hidden_sizes=HIDDEN, concat=True, device=dev,
+                         linear_layer=linear), device=dev, linear_layer=linear,
+                     flatten_input=False).to(dev)
+    log_alpha = torch.zeros(1, requires_grad=True, device=dev)
+    alpha = (-float(A), log_alpha, torch.optim.Adam([log_alpha], lr=3e-4))
+    policy = REDQPolicy(actor, torch.optim.Adam(actor.parameters(), lr=3e-4), critics,
+                        torch.optim.Adam(critics.parameters(), lr=3e-4),
+                        ensemble_size=REDQ_ENSEMBLE, subset_size=REDQ_SUBSET, tau=0.005,
+                        gamma=0.99, alpha=alpha, estimation_step=1,
+                        actor_delay=args.redq_actor_delay, action_scaling=False).to(dev)
+    for k, v in LEGS[leg].items():
+        setattr(policy, k, v)
+    return policy
+
+
+def stats(prefix, ms):
+    ms = np.asarray(ms)
+    return {prefix + "_ms_mean": round(float(ms.mean()), 4),
+            prefix + "_ms_median": round(float(np.median(ms)), 4),
+            prefix + "_ms_min": round(float(ms.min()), 4),
+            prefix + "_ms_max": round(float(ms.max()), 4)}
+
+
 for kind in args.policies.split(","):
     for name in args.configs.split(","):
         cfg = CONFIGS[name]
@@ -135,7 +176,7 @@ for kind in args.policies.split(","):
                 policy = make_policy(kind, cfg, leg)
                 np.random.seed(0)
                 torch.manual_seed(1)
-                ms, last = [], None
+                ms, kinds, last = [], [], None
                 for u in range(args.warmup + args.updates):
                     t0 = torch.cuda.Event(enable_timing=True)
                     t1 = torch.cuda.Event(enable_timing=True)
@@ -145,15 +186,22 @@ for kind in args.policies.split(","):
                     t1.synchronize()
                     if u >= args.warmup:
                         ms.append(t0.elapsed_time(t1))
+                        kinds.append("loss/actor" in last)
                 assert all(np.isfinite(v) for v in last.values())
-                ms = np.asarray(ms)
+                timing = stats("update", ms)
+                if kind == "redq":  # the two step kinds apart
+                    by = {k: [m for m, a in zip(ms, kinds) if a == (k == "actor")]
+                          for k in ("critic", "actor")}
+                    timing.update(stats("critic", by["critic"]))
+                    timing.update(stats("actor", by["actor"]))
+                    timing["critic_updates"], timing["actor_updates"] = \
+                        len(by["critic"]), len(by["actor"])
+                    timing["update_ms_at_delay_20"] = round(
+                        (19 * timing["critic_ms_mean"] + timing["actor_ms_mean"]) / 20, 4)
                 print(json.dumps({
                     "policy": kind, "config": name, "leg": leg, "run": run,
                     "batch": cfg["batch"], "obs": cfg["D"], "act": cfg["A"],
-                    "updates": args.updates, "update_ms_mean": round(float(ms.mean()), 4),
-                    "update_ms_median": round(float(np.median(ms)), 4),
-                    "update_ms_min": round(float(ms.min()), 4),
-                    "update_ms_max": round(float(ms.max()), 4),
+                    "updates": args.updates, **timing,
                     "graphs": len(policy._learn_graphs),
                     "flat_optimiser": bool(policy._flats) and all(
                         policy._flat_ready(n) for n in policy._optim_order),

@@ -2388,13 +2388,245 @@ def gen_dsac():
     _save("dsac.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 25. REDQPolicy (tianshou/policy/modelfree/redq.py) and EnsembleLinear
+#     (tianshou/utils/net/common.py:402-432) over gen_ddpg's add() stream:
+#     (a) the critic ensemble built alone under a seed (EnsembleLinear's initialiser), and one
+#         forward of the policy in eval mode (deterministic) and one in training mode;
+#     (b) six update() calls per variant, recorded as gen_sac records them (the clamped
+#         _standard_normal recorder included).  An update draws the subset of target critics
+#         (np.random.choice(..., replace=False), recorded) and one [batch, A] normal in
+#         process_fn; learn draws a second normal only on the updates that step the actor.
+#         Quantities that exist only on those updates (eps_learn, log_prob, qa, loss_actor,
+#         loss_alpha, alpha) are NaN elsewhere; "did_actor" says which.  The reference returns
+#         loss/actor as a 1-tuple (redq.py:195); its one element is recorded.
+#     Asserted on the reference alone: min(1 - act^2) >= 0.02 over every recorded forward,
+#     each variant's count of actor updates is what its actor_delay implies, and every outgoing
+#     weight mean_e td has magnitude >= REDQ_MIN_TD: they are compared at rtol 1e-4 with no
+#     absolute part, and a TD error is the difference of two f32 numbers of magnitude up to 7,
+#     each a few ulp32 off on another GEMM (gen_dsac's DSAC_MIN_TD, for the same reason).  A
+#     variant that misses one gets another "seed", not a bound.
+# --------------------------------------------------------------------------------------
+REDQ_ENSEMBLE = 5
+REDQ_MIN_TD = 1e-2
+REDQ_VARIANTS = {
+    "redq": dict(auto=False, subset=2, mode="min", delay=2, n_step=1, bs=64, optim="adam",
+                 seed=19),
+    "redq_auto": dict(auto=True, subset=2, mode="min", delay=3, n_step=1, bs=65, optim="adam",
+                      seed=1),
+    "redq_mean": dict(auto=False, subset=3, mode="mean", delay=2, n_step=1, bs=64,
+                      optim="adam", seed=64),
+    "redq_full": dict(auto=True, subset=REDQ_ENSEMBLE, mode="min", delay=1, n_step=1, bs=64,
+                      optim="adam", seed=4),
+    "redq_per": dict(auto=True, subset=2, mode="min", delay=2, n_step=3, bs=32, optim="adam",
+                     per=True, seed=3),
+    "redq_rms": dict(auto=True, subset=2, mode="min", delay=2, n_step=1, bs=64, optim="rms",
+                     seed=2),
+}
+REDQ_NETS = ["actor", "critics"]
+
+
+def _redq_flat_params(policy):
+    """actor, critics, critics_old in named_parameters() order."""
+    mods = [policy.actor, policy.critics, policy.critics_old]
+    return np.concatenate([t.detach().numpy().ravel() for m in mods for t in m.parameters()])
+
+
+def gen_redq():
+    import torch.distributions.normal as tdn
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import REDQPolicy
+    from tianshou.utils.net.common import EnsembleLinear, Net
+    from tianshou.utils.net.continuous import ActorProb, Critic
+    out = {}
+    E, S, D, A, NE = DQN_E, DQN_S, DDPG_D, DDPG_A, REDQ_ENSEMBLE
+    adds = _ddpg_adds(np.random.default_rng(43))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    real_normal, real_choice = tdn._standard_normal, np.random.choice
+    draws, subsets = [], []
+
+    def rec_normal(shape, dtype, device):
+        t = real_normal(shape, dtype=dtype, device=device).clamp(-2.0, 2.0)
+        draws.append(t.numpy().copy())
+        return t
+
+    def rec_choice(*a, **kw):
+        res = real_choice(*a, **kw)
+        if kw.get("replace") is False:  # the subset draw; the buffer samples with replacement
+            subsets.append(np.array(res, copy=True))
+        return res
+
+    def optim_of(kind, params, lr=None):
+        if kind == "rms":
+            return torch.optim.RMSprop(params, lr=lr or 7e-4, eps=1e-5, alpha=0.99)
+        return torch.optim.Adam(params, lr=lr or 1e-3)
+
+    def linear(x, y):
+        return EnsembleLinear(NE, x, y)
+
+    def critics_of():  # examples/mujoco/mujoco_redq.py:92-105
+        return Critic(Net(D, A, hidden_sizes=(16, 16), concat=True, linear_layer=linear),
+                      linear_layer=linear, flatten_input=False)
+
+    # (a) EnsembleLinear's initialiser: the ensemble alone under a seed
+    torch.manual_seed(DDPG_INIT_SEED + 1)
+    out.update(_named_arrays("seeded_critics.", critics_of()))
+
+    tdn._standard_normal, np.random.choice = rec_normal, rec_choice
+    try:
+        for tag, v in REDQ_VARIANTS.items():
+            p = tag + "_"
+            if v.get("per"):
+                buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+            else:
+                buf = VectorReplayBuffer(E * S, E)
+            for a in adds:
+                buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                        buffer_ids=a["ids"])
+            torch.manual_seed(DDPG_INIT_SEED)
+            actor = ActorProb(Net(D, hidden_sizes=(16, 16)), (A,), unbounded=True,
+                              conditioned_sigma=True)
+            critics = critics_of()
+            alpha = SAC_ALPHA
+            if v["auto"]:
+                log_alpha = torch.zeros(1, requires_grad=True)
+                alpha = (-float(A), log_alpha, optim_of(v["optim"], [log_alpha], SAC_ALPHA_LR))
+            policy = REDQPolicy(actor, optim_of(v["optim"], actor.parameters()), critics,
+                                optim_of(v["optim"], critics.parameters()), ensemble_size=NE,
+                                subset_size=v["subset"], tau=DDPG_TAU, gamma=DDPG_GAMMA,
+                                alpha=alpha, estimation_step=v["n_step"],
+                                actor_delay=v["delay"], target_mode=v["mode"],
+                                action_scaling=False)
+            if tag == "redq":  # every variant starts from these weights
+                for name in REDQ_NETS:
+                    out.update(_named_arrays(f"init_{name}.", getattr(policy, name)))
+            else:
+                for name in REDQ_NETS:
+                    for k, x in _named_arrays(f"init_{name}.", getattr(policy, name)).items():
+                        assert np.array_equal(out[k], x), (tag, k)
+            forward, process_fn, learn = policy.forward, policy.process_fn, policy.learn
+            seen, fwd, q_calls = [], [], []
+            min_one_m = [np.inf]
+
+            def rec_forward(batch, *a, **kw):
+                res = forward(batch, *a, **kw)
+                act = res.act.detach().numpy().astype(np.float64)
+                min_one_m[0] = min(min_one_m[0], float((1.0 - act * act).min()))
+                fwd.append(res)
+                return res
+
+            policy.forward = rec_forward
+            hook = policy.critics.register_forward_hook(
+                lambda m, a, o: q_calls.append(o.detach().flatten(1).numpy().copy()))
+            if tag == "redq":
+                out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                    np.asarray(buf.last_index)
+                torch.manual_seed(DDPG_SAMPLE_SEED + 1)
+                obs = adds[0]["obs"]
+                out["fwd_obs"] = obs
+                for mode in ("eval", "train"):
+                    policy.train(mode == "train")
+                    n0 = len(draws)
+                    with torch.no_grad():
+                        res = policy(Batch(obs=obs, info={}))
+                    assert len(draws) - n0 == (mode == "train")
+                    out[f"fwd_{mode}_act"] = res.act.numpy().copy()
+                    out[f"fwd_{mode}_log_prob"] = res.log_prob.numpy().copy()
+                    for i, name in enumerate(("mu", "sigma")):
+                        out[f"fwd_{mode}_{name}"] = res.logits[i].numpy().copy()
+                out["fwd_train_eps"] = draws[-1]
+                with torch.no_grad():  # the Critic construction of mujoco_redq.py: [E, b, 1]
+                    q = policy.critics(obs, adds[0]["act"])
+                assert q.shape == (NE, len(obs), 1)
+                out["fwd_act_in"], out["fwd_q"] = adds[0]["act"], q.numpy().copy()
+                q_calls.clear()
+            policy.train()
+
+            def rec_process(batch, buffer, indices):
+                n0, s0 = len(draws), len(subsets)
+                batch = process_fn(batch, buffer, indices)
+                assert len(draws) - n0 == 1 and draws[-1].shape == (v["bs"], A)
+                assert len(subsets) - s0 == 1 and subsets[-1].shape == (v["subset"],)
+                seen.append(dict(indices=np.array(indices, copy=True), eps_target=draws[-1],
+                                 subset=subsets[-1].astype(np.int64),
+                                 returns=batch.returns.detach().numpy().copy()))
+                if hasattr(batch, "weight"):
+                    seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+                return batch
+
+            def rec_learn(batch, **kw):
+                n0, f0, q0 = len(draws), len(fwd), len(q_calls)
+                row = seen[-1]
+                row["alpha_in"] = np.array(float(policy._alpha), np.float32)
+                res = learn(batch, **kw)
+                did = policy.critic_gradient_step % v["delay"] == 0
+                assert len(draws) - n0 == did and len(fwd) - f0 == did
+                assert len(q_calls) - q0 == 1 + did
+                row["did_actor"] = np.array(did)
+                row["q_obs"] = q_calls[q0]
+                nan = lambda *shape: np.full(shape, np.nan, np.float32)  # noqa: E731
+                row["eps_learn"] = draws[-1] if did else nan(v["bs"], A)
+                row["log_prob"] = fwd[-1].log_prob.detach().numpy().reshape(-1).copy() \
+                    if did else nan(v["bs"])
+                row["qa"] = q_calls[-1] if did else nan(NE, v["bs"])
+                row["td"] = batch.weight.detach().numpy().copy()
+                return res
+
+            policy.process_fn, policy.learn = rec_process, rec_learn
+            np.random.seed(v["seed"])
+            torch.manual_seed(v["seed"])
+            for u in range(6):
+                res = policy.update(v["bs"], buf)
+                row = seen[u]
+                did = bool(row["did_actor"])
+                assert set(res) == {"loss/critics"} | ({"loss/actor"} if did else set()) | (
+                    {"loss/alpha", "alpha"} if did and v["auto"] else set())
+                if did:  # the reference's stray comma
+                    assert isinstance(res["loss/actor"], tuple) and len(res["loss/actor"]) == 1
+                    res["loss/actor"] = res["loss/actor"][0]
+                row["loss_critics"] = np.array(res["loss/critics"])
+                for k in ("loss/actor", "loss/alpha", "alpha"):
+                    row[k.replace("/", "_")] = np.array(res.get(k, np.nan))
+                row["params"] = _redq_flat_params(policy)
+                if v["auto"]:
+                    row["log_alpha"] = policy._log_alpha.detach().numpy().copy()
+                if v.get("per"):
+                    row["leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+            hook.remove()
+            n_actor = sum(bool(r["did_actor"]) for r in seen)
+            assert n_actor == 6 // v["delay"], (tag, n_actor)
+            assert [bool(r["did_actor"]) for r in seen] == \
+                [(u + 1) % v["delay"] == 0 for u in range(6)]
+            assert min_one_m[0] >= 0.02, (tag, min_one_m[0])
+            min_td = min(float(np.abs(r["td"]).min()) for r in seen)
+            assert min_td >= REDQ_MIN_TD, (tag, min_td)
+            print(tag, "actor updates", n_actor, "min(1 - act^2)", min_one_m[0], "min|td|",
+                  min_td, "subsets",
+                  [r["subset"].tolist() for r in seen])
+            for k in seen[0]:  # one array per quantity: the six updates stacked
+                out[p + k] = np.stack([row[k] for row in seen])
+            if v.get("per"):
+                out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                    np.array(buf._min_prio)
+    finally:
+        tdn._standard_normal, np.random.choice = real_normal, real_choice
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=E, S=S, D=D, A=A, gamma=DDPG_GAMMA, tau=DDPG_TAU, hidden=[16, 16],
+        init_seed=DDPG_INIT_SEED + 1, ensemble=NE, min_td=REDQ_MIN_TD, alpha=SAC_ALPHA,
+        alpha_lr=SAC_ALPHA_LR, target_entropy=-float(A), variants=REDQ_VARIANTS,
+        nets=REDQ_NETS)))
+    _save("redq.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "a2c", "dqn", "dist_dqn", "ddpg", "sac",
-                             "dsac"]
+                             "dsac", "redq"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -2402,6 +2634,7 @@ if __name__ == "__main__":
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
                  persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn,
-                 dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac)
+                 dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
+                 redq=gen_redq)
     for w in which:
         table[w]()
