@@ -733,6 +733,56 @@ int tsrl_nstep_return(const double* rew, const uint8_t* done, const uint8_t* ter
                       int64_t num, const int64_t* idx, int64_t bsz, int64_t n_step,
                       double gamma, const void* target_q, int64_t X, int f64, void* out,
                       void* stream);
+/* tsrl_replay_sample: one launch for everything an n-step off-policy update reads from the
+ *   buffer.  For each of bsz sampled rows, with c0 = idx[b] mod (size*num) and
+ *   c_i = next(c_{i-1}): the gathered stored row c0 (obs, act, rew, flags, env id; dense
+ *   outputs, the observation storage possibly pitched), its one-step next observation
+ *   (obs_next_out, nullable), terminal_out[b] = c_{n_step-1} and the next observation at that
+ *   row (the input of every target network), ret_out[b] = the discounted reward sum of
+ *   tsrl_nstep_return and coef_out[b] = gamma^gammas, or 0 where the terminal row is
+ *   terminated.  obs_next == NULL (a buffer built with ignore_obs_next): both next
+ *   observations are obs at next(), as ReplayBuffer.__getitem__ (base.py:380-381).
+ *   term_obs_next_out may equal obs_next_out when n_step == 1.  1 <= n_step <= 64.
+ * tsrl_nstep_apply: out[b][x] = target_q[b][x] * coef[b] + ret[b] in f64, rounded to the
+ *   target dtype (f64 != 0: double, else float).  tsrl_replay_sample + tsrl_nstep_apply equal
+ *   tsrl_nstep_return bit for bit for finite targets. */
+typedef struct tsrl_replay_sample_args {
+    const int64_t* idx;
+    int64_t bsz;
+    /* ring (see tsrl_ring_step_index) */
+    const uint8_t* done;
+    const int64_t* last_index;
+    const int64_t* lengths;
+    int64_t size, num;
+    int64_t n_step;
+    double gamma;
+    /* storage: obs / obs_next rows obs_pitch bytes apart, obs_row_bytes long */
+    const char* obs;
+    const char* obs_next; /* NULL: not stored */
+    int64_t obs_pitch, obs_row_bytes;
+    const char* act;
+    int64_t act_row_bytes;
+    const double* rew;
+    const uint8_t* terminated;
+    const uint8_t* truncated;
+    const int64_t* env_id;
+    /* outputs, bsz dense rows each */
+    char* obs_out;
+    char* act_out;
+    double* rew_out;
+    uint8_t* terminated_out;
+    uint8_t* truncated_out;
+    uint8_t* done_out;
+    int64_t* env_id_out;
+    char* obs_next_out; /* nullable */
+    int64_t* terminal_out;
+    char* term_obs_next_out;
+    double* ret_out;
+    double* coef_out;
+} tsrl_replay_sample_args;
+int tsrl_replay_sample(const tsrl_replay_sample_args* a, void* stream);
+int tsrl_nstep_apply(const void* target_q, const double* coef, const double* ret, int64_t bsz,
+                     int64_t X, int f64, void* out, void* stream);
 int tsrl_segtree_set(double* tree, int64_t bound, const int64_t* idx, const double* values,
                      int64_t value_stride, int64_t k, int* win, void* stream);
 int tsrl_segtree_reduce(const double* tree, int64_t bound, int64_t start, int64_t end,

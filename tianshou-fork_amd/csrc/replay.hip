@@ -17,6 +17,17 @@
 //          reduce (_reduce, :107-119): the reference's exact summation order, one thread.
 //          prefix (_get_prefix_sum_idx, :122-137): one descent per query value; f32 query
 //                 arrays keep numpy's in-place f32 rounding after every subtraction.
+// sample : everything an n-step off-policy update reads from the buffer, in one launch
+//          (BasePolicy.update's sample + process_fn side: ReplayBuffer.__getitem__,
+//          base.py:360-389, and the index half of compute_nstep_return).  One wave per sampled
+//          row.  The whole wave walks the next() chain redundantly (uniform addresses, no
+//          divergence); lane n keeps chain row n, so the n_step reward loads and end flags are
+//          one parallel load per lane instead of a private 64-entry array, and the backward
+//          recurrence reads them back lane by lane (shuffle + ballot).  The wave then copies
+//          the payload rows (copy_row) and lane 0 writes the scalars.  At batch 256 that is 64
+//          workgroups: the launch is latency-bound by the chain's dependent loads.
+// apply  : out = target_q * coef + ret, the value half of nstep_kernel, with no index input.
+#include "add_row.h"
 #include "ring.h"
 
 namespace tsrl {
@@ -58,6 +69,86 @@ __global__ __launch_bounds__(TPB) void nstep_kernel(Ring g, const double* __rest
     double gp = 1.0;  // gamma_buffer[gammas]: repeated products, as base.py:509-511
     for (int i = 1; i <= gammas; ++i) gp = gp * gamma;
     out[t] = (T)((double)q * gp + ret);
+}
+
+static_assert(MAX_NSTEP <= kWave, "replay_sample keeps one chain row per lane");
+constexpr int ROWS_PER_BLOCK = TPB / kWave;  // one wave per sampled row
+
+__global__ __launch_bounds__(TPB) void replay_sample_kernel(tsrl_replay_sample_args a) {
+#pragma clang fp contract(off)
+    const Ring g = {a.done, a.last_index, a.lengths, a.size, a.size * a.num};
+    const int lane = threadIdx.x & (kWave - 1);
+    const int n_step = (int)a.n_step;
+    const double gamma = a.gamma;
+    const int64_t nw = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+    for (int64_t b = (int64_t)blockIdx.x * ROWS_PER_BLOCK + threadIdx.x / kWave; b < a.bsz;
+         b += nw) {
+        const int64_t c0 = pmod(a.idx[b], g.maxsize);
+        int64_t c = c0, mine = c0;
+        for (int n = 1; n < n_step; ++n) {
+            c = ring_next(g, c);
+            if (lane == n) mine = c;
+        }
+        const int64_t term = c;  // chain[n_step - 1]
+        // lane n < n_step: reward and end flag of chain row n (other lanes: row c0, unused)
+        const double my_rew = a.rew[mine];
+        const unsigned long long ends = __ballot(lane < n_step && ring_end(g, mine));
+        double ret = 0.0;
+        int gammas = n_step;
+        for (int n = n_step - 1; n >= 0; --n) {
+            const double r = __shfl(my_rew, n, kWave);
+            if ((ends >> n) & 1ull) {
+                gammas = n + 1;
+                ret = 0.0;
+            }
+            ret = r + gamma * ret;  // two roundings: fp contract(off) above
+        }
+        double gp = 1.0;  // gamma_buffer[gammas]: repeated products, as base.py:509-511
+        for (int i = 1; i <= gammas; ++i) gp = gp * gamma;
+
+        // payload rows
+        copy_row(a.obs + c0 * a.obs_pitch, a.obs_out + b * a.obs_row_bytes, a.obs_row_bytes,
+                 lane);
+        copy_row(a.act + c0 * a.act_row_bytes, a.act_out + b * a.act_row_bytes,
+                 a.act_row_bytes, lane);
+        // next observations: the stored obs_next row, or obs at next() (base.py:380-381)
+        if (a.obs_next_out) {
+            const char* src = a.obs_next ? a.obs_next + c0 * a.obs_pitch
+                                         : a.obs + ring_next(g, c0) * a.obs_pitch;
+            copy_row(src, a.obs_next_out + b * a.obs_row_bytes, a.obs_row_bytes, lane);
+        }
+        if (a.term_obs_next_out != a.obs_next_out || n_step > 1) {
+            const char* src = a.obs_next ? a.obs_next + term * a.obs_pitch
+                                         : a.obs + ring_next(g, term) * a.obs_pitch;
+            copy_row(src, a.term_obs_next_out + b * a.obs_row_bytes, a.obs_row_bytes, lane);
+        }
+        if (lane == 0) {
+            a.rew_out[b] = a.rew[c0];
+            a.terminated_out[b] = a.terminated[c0];
+            a.truncated_out[b] = a.truncated[c0];
+            a.done_out[b] = a.done[c0];
+            a.env_id_out[b] = a.env_id[c0];
+            a.terminal_out[b] = term;
+            a.ret_out[b] = ret;
+            // value mask of the terminal row (base.py:432) folded into the bootstrap factor; the
+            // zero keeps gp's sign so that target_q * coef has the sign of
+            // (target_q * 0) * gp, as nstep_kernel forms it
+            a.coef_out[b] = a.terminated[term] ? __builtin_copysign(0.0, gp) : gp;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(TPB) void nstep_apply_kernel(const T* __restrict__ target_q,
+                                                          const double* __restrict__ coef,
+                                                          const double* __restrict__ ret,
+                                                          int64_t bsz, int64_t X,
+                                                          T* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (t >= bsz * X) return;
+    const int64_t b = t / X;
+    out[t] = (T)((double)target_q[t] * coef[b] + ret[b]);
 }
 
 // win: int32 scratch of one entry per leaf, all -1 on entry (restored on exit).
@@ -146,6 +237,49 @@ extern "C" int tsrl_nstep_return(const double* rew, const uint8_t* done,
                            reinterpret_cast<const float*>(target_q), X,
                            reinterpret_cast<float*>(out));
     TSRL_LAUNCH_CHECK("tsrl_nstep_return");
+    return 0;
+}
+
+extern "C" int tsrl_replay_sample(const tsrl_replay_sample_args* a, void* stream) {
+    TSRL_CHECK_ARG(a != nullptr, "tsrl_replay_sample: null args");
+    TSRL_CHECK_ARG(a->bsz >= 0 && a->n_step >= 1 && a->n_step <= MAX_NSTEP,
+                   "tsrl_replay_sample: bad sizes (bsz >= 0, 1 <= n_step <= %d)", MAX_NSTEP);
+    if (a->bsz == 0) return 0;
+    TSRL_CHECK_ARG(a->idx && a->done && a->last_index && a->lengths && a->obs && a->act &&
+                       a->rew && a->terminated && a->truncated && a->env_id,
+                   "tsrl_replay_sample: null input pointer");
+    TSRL_CHECK_ARG(a->obs_out && a->act_out && a->rew_out && a->terminated_out &&
+                       a->truncated_out && a->done_out && a->env_id_out && a->terminal_out &&
+                       a->term_obs_next_out && a->ret_out && a->coef_out,
+                   "tsrl_replay_sample: null output pointer");
+    TSRL_CHECK_ARG(a->size > 0 && a->num > 0, "tsrl_replay_sample: empty buffer");
+    TSRL_CHECK_ARG(a->obs_row_bytes > 0 && a->obs_pitch >= a->obs_row_bytes &&
+                       a->act_row_bytes > 0,
+                   "tsrl_replay_sample: bad row sizes");
+    TSRL_CHECK_ARG(a->term_obs_next_out != a->obs_next_out || a->n_step == 1,
+                   "tsrl_replay_sample: the next-observation outputs may alias only at n_step 1");
+    const int64_t grid = std::min<int64_t>((a->bsz + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, 16384);
+    hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)grid), dim3(TPB), 0,
+                       as_stream(stream), *a);
+    TSRL_LAUNCH_CHECK("tsrl_replay_sample");
+    return 0;
+}
+
+extern "C" int tsrl_nstep_apply(const void* target_q, const double* coef, const double* ret,
+                                int64_t bsz, int64_t X, int f64, void* out, void* stream) {
+    TSRL_CHECK_ARG(bsz >= 0 && X >= 1, "tsrl_nstep_apply: bad sizes (bsz >= 0, X >= 1)");
+    if (bsz == 0) return 0;
+    TSRL_CHECK_ARG(target_q && coef && ret && out, "tsrl_nstep_apply: null pointer");
+    const unsigned grid = (unsigned)((bsz * X + TPB - 1) / TPB);
+    if (f64)
+        hipLaunchKernelGGL(nstep_apply_kernel<double>, dim3(grid), dim3(TPB), 0,
+                           as_stream(stream), reinterpret_cast<const double*>(target_q), coef,
+                           ret, bsz, X, reinterpret_cast<double*>(out));
+    else
+        hipLaunchKernelGGL(nstep_apply_kernel<float>, dim3(grid), dim3(TPB), 0,
+                           as_stream(stream), reinterpret_cast<const float*>(target_q), coef, ret,
+                           bsz, X, reinterpret_cast<float*>(out));
+    TSRL_LAUNCH_CHECK("tsrl_nstep_apply");
     return 0;
 }
 

@@ -60,6 +60,20 @@ class CollectArgs(ctypes.Structure):
     ]
 
 
+class ReplaySampleArgs(ctypes.Structure):
+    """Mirror of ``tsrl_replay_sample_args`` (field order must match include/tsrl.h)."""
+    _fields_ = [
+        ("idx", _p), ("bsz", _i64), ("done", _p), ("last_index", _p), ("lengths", _p),
+        ("size", _i64), ("num", _i64), ("n_step", _i64), ("gamma", _d),
+        ("obs", _p), ("obs_next", _p), ("obs_pitch", _i64), ("obs_row_bytes", _i64),
+        ("act", _p), ("act_row_bytes", _i64), ("rew", _p), ("terminated", _p),
+        ("truncated", _p), ("env_id", _p),
+        ("obs_out", _p), ("act_out", _p), ("rew_out", _p), ("terminated_out", _p),
+        ("truncated_out", _p), ("done_out", _p), ("env_id_out", _p), ("obs_next_out", _p),
+        ("terminal_out", _p), ("term_obs_next_out", _p), ("ret_out", _p), ("coef_out", _p),
+    ]
+
+
 class PPOParams(ctypes.Structure):
     """Mirror of ``tsrl_ppo_params``."""
     _fields_ = [
@@ -157,6 +171,8 @@ _SIGS = {
     "tsrl_dqn_conv1_wgrad": ([_p, _i64, _p, _p, _f, _p, _p, _p, _i64, _p], ctypes.c_int),
     "tsrl_nstep_return": ([_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _d, _p, _i64,
                            ctypes.c_int, _p, _p], ctypes.c_int),
+    "tsrl_replay_sample": ([ctypes.POINTER(ReplaySampleArgs), _p], ctypes.c_int),
+    "tsrl_nstep_apply": ([_p, _p, _p, _i64, _i64, ctypes.c_int, _p, _p], ctypes.c_int),
     "tsrl_clip_adam_partials": ([_i64], _i64),
     "tsrl_clip_adam": ([_p, _p, _p, _p, _i64, _p, _i64, _f, _f, _f, _f, _f, _p, _p, _p, _p,
                         ctypes.POINTER(W1Split), ctypes.c_int, _p],

@@ -3,4 +3,4 @@ Collector -> device VectorReplayBuffer -> GAE -> PPOPolicy.learn, with the refer
 class API on top of the libtsrl HIP kernels (include/tsrl.h)."""
 __version__ = "0.1.0"
 
-from tianshou_amd import data, env, policy, utils  # noqa: F401,E402
+from tianshou_amd import data, env, policy, trainer, utils  # noqa: F401,E402

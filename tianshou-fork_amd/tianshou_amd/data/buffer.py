@@ -105,10 +105,39 @@ class RingIndex:
         return bool(np.all(self.lengths == self.size) and np.all(self.index == 0))
 
 
+class NstepToken:
+    """The terminal rows next^(n_step-1)(indices) of one fused sample
+    (``VectorReplayBuffer.sample_nstep``), handed to a policy's ``target_q_fn`` in place of the
+    NumPy indices: ``buffer.get(token, "obs_next")`` and ``buffer[token].obs_next`` return the
+    rows the sample kernel gathered already, every other key is gathered at the device
+    indices, and ``np.asarray(token)`` still yields the indices (the only device-to-host
+    copy, made when someone asks for it)."""
+
+    def __init__(self, terminal: torch.Tensor, obs_next: torch.Tensor) -> None:
+        self.terminal = terminal
+        self.obs_next = obs_next
+
+    def __len__(self) -> int:
+        return int(self.terminal.numel())
+
+    def __array__(self, dtype=None, copy=None) -> np.ndarray:
+        arr = self.terminal.cpu().numpy()
+        return arr if dtype is None else arr.astype(dtype, copy=False)
+
+
+class _NstepParts:
+    """What the last fused sample left for compute_nstep_return (see sample_nstep)."""
+    __slots__ = ("indices", "n_step", "gamma", "token", "ret", "coef", "ring_last")
+
+
 class VectorReplayBuffer:
     """VectorReplayBuffer(total_size, buffer_num) in HBM (vecbuf.py:15-37)."""
 
     _reserved_keys = _RESERVED
+    fused_samples = 0    # sample_nstep calls that took the one-launch tsrl_replay_sample
+    _nstep_parts = None  # the parts of the last of them (one-shot, see take_nstep_parts)
+    _ring_cache = None   # (host last_index, host lengths, device last_index, device lengths)
+    _nstep_ok_meta = None
     # f32 observation rows wider than this many floats get a 128-byte-multiple storage pitch
     # (see _alloc_storage); None-like large value disables the padding
     PAD_MIN = 96
@@ -293,7 +322,8 @@ class VectorReplayBuffer:
                 return {"__batch__": {k: host(x) for k, x in v.items()}}
             return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v
         st = {k: v for k, v in self.__dict__.items()
-              if k not in ("_meta", "_dev", "_last_sample0", "device")}
+              if k not in ("_meta", "_dev", "_last_sample0", "device", "_nstep_parts",
+                           "_ring_cache", "_nstep_ok_meta")}
         st["_meta"] = host(self._meta)
         st["_dev"] = None if self._dev is None else {k: host(v) for k, v in self._dev.items()}
         return st
@@ -509,9 +539,118 @@ class VectorReplayBuffer:
         indices = self.sample_indices(batch_size)
         return self[indices], indices
 
+    # -- fused n-step sample ---------------------------------------------------------------------
+    def _can_sample_nstep(self) -> bool:
+        """Whether tsrl_replay_sample can serve this buffer: one frame per row, plain tensor
+        storage on the device, obs and obs_next laid out alike."""
+        m = self._meta
+        if self._nstep_ok_meta is m:
+            return True
+        if self.stack_num != 1 or m.is_empty():
+            return False
+        need = ("obs", "act", "rew", "terminated", "truncated", "done")
+        if any(not isinstance(m.get(k), torch.Tensor) or not m[k].is_cuda for k in need):
+            return False
+        env_id = m.info.get("env_id") if isinstance(m.get("info"), Batch) else None
+        if not isinstance(env_id, torch.Tensor) or env_id.dtype != torch.int64:
+            return False
+        obs = m.obs
+        rows_ok = obs.is_contiguous() or (obs.dim() == 2 and obs.stride(1) == 1
+                                          and obs.stride(0) >= obs.shape[1])
+        if not rows_ok or not m.act.is_contiguous() or m.rew.dtype != torch.float64 or \
+                any(m[k].dtype != torch.bool for k in ("terminated", "truncated", "done")):
+            return False
+        if self._save_obs_next:
+            nxt = m.get("obs_next")
+            if not isinstance(nxt, torch.Tensor) or nxt.dtype != obs.dtype or \
+                    nxt.shape != obs.shape or nxt.stride() != obs.stride():
+                return False
+        self._nstep_ok_meta = m
+        return True
+
+    def sample_nstep(self, batch_size: int, n_step: int, gamma: float
+                     ) -> Tuple[Batch, np.ndarray]:
+        """``sample(batch_size)`` for an n-step off-policy update: the same (batch, indices),
+        gathered by one tsrl_replay_sample launch that also leaves what
+        ``BasePolicy.compute_nstep_return(batch, buffer, indices, ..., gamma, n_step)`` needs
+        -- the terminal rows, their next observations, the discounted reward sums and the
+        bootstrap factors -- on the device for that call (recognised by the identity of
+        ``indices``).  Where the kernel cannot serve the buffer (frame stacks, Batch-valued
+        observations, batch_size <= 0) this is ``sample``."""
+        indices = self.sample_indices(batch_size)
+        if batch_size <= 0 or len(indices) == 0 or not self._can_sample_nstep():
+            return self[indices], indices
+        return self._gather_nstep(indices, int(n_step), float(gamma)), indices
+
+    def _gather_nstep(self, indices: np.ndarray, n_step: int, gamma: float) -> Batch:
+        m, dev = self._meta, self.device
+        it = self._index_tensor(indices)
+        bsz = it.numel()
+        obs_st, act_st = m.obs, m.act
+
+        def rows(st):
+            return torch.empty((bsz,) + tuple(st.shape[1:]), dtype=st.dtype, device=dev)
+
+        def vec(dtype):
+            return torch.empty(bsz, dtype=dtype, device=dev)
+        obs, act, obs_next = rows(obs_st), rows(act_st), rows(obs_st)
+        term_next = obs_next if n_step == 1 else rows(obs_st)
+        rew, ret, coef = vec(torch.float64), vec(torch.float64), vec(torch.float64)
+        terminated, truncated, done = vec(torch.bool), vec(torch.bool), vec(torch.bool)
+        env_id, terminal = vec(torch.int64), vec(torch.int64)
+        done_st, last, lengths = self._ring_dev()
+        a = _C.ReplaySampleArgs()
+        a.idx, a.bsz = _C.ptr(it), bsz
+        a.done, a.last_index, a.lengths = _C.ptr(done_st), _C.ptr(last), _C.ptr(lengths)
+        a.size, a.num = self._ring.size, self.buffer_num
+        a.n_step, a.gamma = n_step, gamma
+        esz = obs_st.element_size()
+        a.obs = _C.ptr_rows(obs_st)
+        a.obs_next = _C.ptr_rows(m.obs_next) if self._save_obs_next else None
+        a.obs_row_bytes = esz * int(np.prod(obs_st.shape[1:]))
+        a.obs_pitch = obs_st.stride(0) * esz if obs_st.dim() >= 2 else esz
+        a.act = _C.ptr(act_st)
+        a.act_row_bytes = act_st.element_size() * int(np.prod(act_st.shape[1:]))
+        a.rew, a.terminated, a.truncated = _C.ptr(m.rew), _C.ptr(m.terminated), \
+            _C.ptr(m.truncated)
+        a.env_id = _C.ptr(m.info.env_id)
+        a.obs_out, a.act_out, a.rew_out = _C.ptr(obs), _C.ptr(act), _C.ptr(rew)
+        a.terminated_out, a.truncated_out, a.done_out = _C.ptr(terminated), \
+            _C.ptr(truncated), _C.ptr(done)
+        a.env_id_out, a.obs_next_out = _C.ptr(env_id), _C.ptr(obs_next)
+        a.terminal_out, a.term_obs_next_out = _C.ptr(terminal), _C.ptr(term_next)
+        a.ret_out, a.coef_out = _C.ptr(ret), _C.ptr(coef)
+        _C.check(_C.lib().tsrl_replay_sample(a, _C.stream_ptr(dev)), "tsrl_replay_sample")
+        info = Batch({k: env_id if k == "env_id" else gather_rows(v, it)
+                      for k, v in m.info.items() if isinstance(v, torch.Tensor)})
+        pol = m.get("policy", Batch())
+        policy = Batch({k: gather_rows(v, it) for k, v in pol.items()
+                        if isinstance(v, torch.Tensor)}) if not pol.is_empty() else Batch()
+        p = _NstepParts()
+        p.indices, p.n_step, p.gamma = indices, n_step, gamma
+        p.token, p.ret, p.coef, p.ring_last = NstepToken(terminal, term_next), ret, coef, last
+        self._nstep_parts = p
+        self.fused_samples += 1
+        return Batch(obs=obs, act=act, rew=rew, terminated=terminated, truncated=truncated,
+                     done=done, obs_next=obs_next, info=info, policy=policy)
+
+    def take_nstep_parts(self, indices, n_step: int, gamma: float):
+        """The parts of the fused sample that handed out ``indices`` (that very array), if it
+        was made with this n_step and gamma and the ring has not moved since; else None.
+        One-shot: the parts are dropped either way."""
+        p, self._nstep_parts = self._nstep_parts, None
+        if p is None or p.indices is not indices or p.n_step != int(n_step) or \
+                p.gamma != float(gamma) or p.ring_last is not self._ring_dev()[1]:
+            return None
+        return p
+
     def __getitem__(self, index) -> Batch:
         """base.py:360-389.  With stack_num > 1, obs / obs_next / info / policy come back
         stacked [k, stack_num, ...] through the device prev chain (tsrl_stack_gather)."""
+        if isinstance(index, NstepToken):
+            if self.stack_num > 1 or self._meta.is_empty():
+                return self[np.asarray(index)]
+            return self._gather_it(index.terminal, obs_next=index.obs_next)
         if isinstance(index, slice):
             indices = self.sample_indices(0) if index == slice(None) \
                 else self._indices[:len(self)][index]
@@ -535,8 +674,14 @@ class VectorReplayBuffer:
             return Batch(obs=obs, act=m.act, rew=m.rew, terminated=m.terminated,
                          truncated=m.truncated, done=m.done, obs_next=obs_next,
                          info=Batch(env_id=m.info.env_id), policy=m.get("policy", Batch()))
-        it = self._index_tensor(indices)
-        if self._save_obs_next:
+        return self._gather_it(self._index_tensor(indices))
+
+    def _gather_it(self, it: torch.Tensor, obs_next=None) -> Batch:
+        """The stored rows at device indices ``it`` (obs_next: rows gathered already)."""
+        m = self._meta
+        if obs_next is not None:
+            pass
+        elif self._save_obs_next:
             obs_next = gather_rows(m.obs_next, it)
         else:
             obs_next = gather_rows(m.obs, self._step_dev(it, -1))
@@ -560,9 +705,17 @@ class VectorReplayBuffer:
 
     # -- episode-aware index stepping and frame stacking (device) -----------------------------
     def _ring_dev(self):
-        dev = self.device
-        return (self._meta.done, torch.as_tensor(self._ring.last_index, device=dev),
-                torch.as_tensor(self._ring.lengths, device=dev))
+        """(done, last_index, lengths) on the device.  The two small uploads are made once
+        per buffer write: they are kept until the host ring differs from what was uploaded."""
+        ring, c = self._ring, self._ring_cache
+        if c is None or not (np.array_equal(c[0], ring.last_index) and
+                             np.array_equal(c[1], ring.lengths)):
+            dev = self.device
+            host_last, host_len = ring.last_index.copy(), ring.lengths.copy()
+            c = (host_last, host_len, torch.as_tensor(host_last, device=dev),
+                 torch.as_tensor(host_len, device=dev))
+            self._ring_cache = c
+        return self._meta.done, c[2], c[3]
 
     def _step_dev(self, it: torch.Tensor, steps: int) -> torch.Tensor:
         """prev^steps (steps > 0) / next^-steps (steps < 0) of device indices
@@ -617,7 +770,12 @@ class VectorReplayBuffer:
         val = self._meta[key]
         if stack_num is None:
             stack_num = self.stack_num
-        it = self._index_tensor(index)
+        if isinstance(index, NstepToken):
+            if key == "obs_next" and stack_num == 1:
+                return index.obs_next
+            it = index.terminal
+        else:
+            it = self._index_tensor(index)
         if stack_num == 1:
             if isinstance(val, Batch):
                 return Batch({k: gather_rows(v, it) for k, v in val.items()

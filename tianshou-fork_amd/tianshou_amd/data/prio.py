@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from tianshou_amd.data.batch import Batch
-from tianshou_amd.data.buffer import ReplayBuffer, VectorReplayBuffer
+from tianshou_amd.data.buffer import NstepToken, ReplayBuffer, VectorReplayBuffer
 from tianshou_amd.data.segtree import SegmentTree
 
 
@@ -110,9 +110,22 @@ class _PrioritizedMixin:
         else:
             indices = index
         batch = super().__getitem__(indices)
+        return self._with_weight(batch, indices.terminal if isinstance(indices, NstepToken)
+                                 else indices)
+
+    def _with_weight(self, batch: Batch, indices) -> Batch:
         weight = self.get_weight_dev(indices)
         batch.weight = weight / weight.max() if self._weight_norm and weight.numel() else weight
         return batch
+
+    def sample_nstep(self, batch_size: int, n_step: int, gamma: float
+                     ) -> Tuple[Batch, np.ndarray]:
+        """The fused sample of the plain buffers plus ``weight``, as ``sample`` returns it."""
+        before = self.fused_samples
+        batch, indices = super().sample_nstep(batch_size, n_step, gamma)
+        if self.fused_samples != before:  # else: sample()'s own __getitem__ added the weight
+            batch = self._with_weight(batch, indices)
+        return batch, indices
 
     def set_beta(self, beta: float) -> None:
         self._beta = beta

@@ -63,6 +63,11 @@ def _as_dev(x, dev, dtype=None):
 
 
 class BasePolicy(nn.Module):
+    # update() of a policy with an ``_n_step`` samples through buffer.sample_nstep (one
+    # tsrl_replay_sample launch, no device-to-host copy before learn()); False: the generic
+    # buffer.sample + compute_nstep_return path.  Both give the same bits.
+    fused_sample = True
+
     def __init__(self, observation_space=None, action_space=None, action_scaling: bool = False,
                  action_bound_method: Optional[Literal["clip", "tanh"]] = None,
                  lr_scheduler=None) -> None:
@@ -172,7 +177,15 @@ class BasePolicy(nn.Module):
         """base.py:288-315."""
         if buffer is None:
             return {}
-        batch, indices = buffer.sample(sample_size)
+        n_step = getattr(self, "_n_step", None)
+        if self.fused_sample and sample_size > 0 and n_step and \
+                not getattr(self, "_rew_norm", False) and hasattr(buffer, "sample_nstep") and \
+                buffer._can_sample_nstep():
+            # n-step off-policy update: the sample and the index half of process_fn's
+            # compute_nstep_return in one launch (csrc/replay.hip); same batch, same indices
+            batch, indices = buffer.sample_nstep(sample_size, n_step, self._gamma)
+        else:
+            batch, indices = buffer.sample(sample_size)
         self.updating = True
         batch = self.process_fn(batch, buffer, indices)
         result = self.learn(batch, **kwargs)
@@ -245,6 +258,26 @@ class BasePolicy(nn.Module):
             "Reward normalization in computing n-step returns is unsupported now."
         bsz = len(indice)
         dev = buffer._ensure_device()
+        parts = buffer.take_nstep_parts(indice, n_step, gamma) \
+            if hasattr(buffer, "take_nstep_parts") else None
+        if parts is not None:
+            # ``indice`` came from buffer.sample_nstep with this n_step and gamma: the terminal
+            # rows, their obs_next, the reward sums and gamma^k are on the device already
+            with torch.no_grad():
+                target_q_torch = target_q_fn(buffer, parts.token)  # (bsz, ?)
+            tq = target_q_torch.reshape(bsz, -1)
+            f64 = tq.dtype == torch.float64
+            tq_dev = tq.to(device=dev, dtype=torch.float64 if f64 else torch.float32
+                           ).contiguous()
+            out = torch.empty_like(tq_dev)
+            _C.check(_C.lib().tsrl_nstep_apply(
+                _C.ptr(tq_dev), _C.ptr(parts.coef), _C.ptr(parts.ret), bsz, tq_dev.shape[1],
+                int(f64), _C.ptr(out), _C.stream_ptr(dev)), "tsrl_nstep_apply")
+            batch.returns = out.to(device=target_q_torch.device, dtype=target_q_torch.dtype)
+            if hasattr(batch, "weight"):  # prio buffer update
+                batch.weight = torch.as_tensor(batch.weight).to(
+                    device=target_q_torch.device, dtype=target_q_torch.dtype)
+            return batch
         it = buffer._index_tensor(indice)
         terminal = buffer._step_dev(it, -(n_step - 1)) if n_step > 1 else \
             buffer._step_dev(it, 0)

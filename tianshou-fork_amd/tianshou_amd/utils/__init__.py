@@ -1,4 +1,4 @@
-from tianshou_amd.utils.statistics import (DeviceRunningMeanStd, DeviceScalarRMS,
+from tianshou_amd.utils.statistics import (DeviceRunningMeanStd, DeviceScalarRMS, MovAvg,
                                            RunningMeanStd)
 
-__all__ = ["RunningMeanStd", "DeviceRunningMeanStd", "DeviceScalarRMS"]
+__all__ = ["MovAvg", "RunningMeanStd", "DeviceRunningMeanStd", "DeviceScalarRMS"]

@@ -14,6 +14,34 @@ import torch
 from tianshou_amd import _C
 
 
+class MovAvg:
+    """Mean and standard deviation over the last ``size`` finite values added
+    (statistics.py:8-66; the trainers' loss statistics).  ``add`` takes a scalar, a sequence
+    of scalars or a tensor, skips infinities and NaN, and returns the new mean."""
+
+    def __init__(self, size: int = 100) -> None:
+        self.size = size
+        self.cache = []
+
+    def add(self, data_array) -> float:
+        if isinstance(data_array, torch.Tensor):
+            data_array = data_array.detach().flatten().cpu().numpy()
+        values = [data_array] if np.isscalar(data_array) else data_array
+        self.cache.extend(x for x in values if np.isfinite(x))
+        if self.size > 0:
+            del self.cache[:-self.size]
+        return self.get()
+
+    def get(self) -> float:
+        return float(np.mean(self.cache)) if self.cache else 0.0
+
+    def mean(self) -> float:
+        return self.get()
+
+    def std(self) -> float:
+        return float(np.std(self.cache)) if self.cache else 0.0
+
+
 class RunningMeanStd:
     """Host RunningMeanStd (statistics.py:69-114): Chan parallel merge, clip on norm."""
 

@@ -2620,20 +2620,211 @@ def gen_redq():
     _save("redq.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# The trainers themselves (tianshou/trainer/base.py:22-563, trainer/utils.py:11-98) driven by
+# the scripted collector and policy of tests/trainer_script.py: the ordered call log, every
+# epoch's (stat, info) without the time fields, the final state, and run()'s result and log.
+# --------------------------------------------------------------------------------------
+def gen_trainer_script():
+    from tianshou.trainer import OffpolicyTrainer, OnpolicyTrainer
+    from tests import trainer_script as ts
+    classes = {"off": OffpolicyTrainer, "on": OnpolicyTrainer}
+    out = {}
+    for name in ts.VARIANTS:
+        kind, kw, log = ts.build(name)
+        epochs, tr = ts.drive(classes[kind], kw)
+        final = dict(epoch=tr.epoch, env_step=tr.env_step, gradient_step=tr.gradient_step,
+                     best_epoch=tr.best_epoch, best_reward=tr.best_reward,
+                     best_reward_std=tr.best_reward_std, stop_fn_flag=tr.stop_fn_flag)
+        kind, kw, run_log = ts.build(name)
+        info = classes[kind](**kw).run()
+        out[name] = dict(log=ts.plain(log), epochs=epochs, final=ts.plain(final),
+                         run=ts.plain({k: v for k, v in info.items() if k not in ts.TIMED}),
+                         run_log=ts.plain(run_log))
+        calls = [(o, m) for o, m, _ in log]
+        print(name, "epochs", len(epochs), "calls", len(log), "updates",
+              calls.count(("policy", "update")), "final", final)
+        # the script reaches the branch the variant is named after
+        spe, me, last = kw["step_per_epoch"], kw["max_epoch"], epochs[-1]["epoch"]
+        upd = [k for o, m, k in log if (o, m) == ("policy", "update")]
+        col = [k for o, m, k in log if (o, m) == ("train", "collect")]
+        if name.startswith("off_ups"):
+            n_st, ups = kw["step_per_collect"], kw["update_per_step"]
+            assert len(upd) == len(col) * round(ups * n_st) and not tr.stop_fn_flag
+            assert round(ups * n_st) == {1.0: 8, 0.25: 2, 2.5: 12}[ups]  # 2.5, 12.5: to even
+        if name in ("off_episode", "on_episode"):
+            assert all(k == dict(n_step=None, n_episode=kw["episode_per_collect"]) for k in col)
+            assert tr.env_step > me * spe  # whole episodes: a collect overshoots an epoch
+        if name == "off_stop_in_train":
+            assert tr.stop_fn_flag and last < me and tr.env_step % spe != 0
+            # ... after a middle test that did not pass: policy.train() follows its collect
+            i = max(i for i, c in enumerate(calls[:-2]) if c == ("test", "collect")
+                    and calls[i + 1:i + 3] == [("hook", "stop_fn"), ("policy", "train")])
+            assert calls[i - 1] == ("hook", "test_fn") and log[i - 1][2]["env_step"] % spe != 0
+            assert "test_reward" not in epochs[-1]["stat"]
+        if name == "off_stop_at_test":
+            assert tr.stop_fn_flag and last < me and tr.env_step == last * spe
+            assert epochs[-1]["stat"]["best_epoch"] == last
+        if name == "off_no_test":
+            assert ("test", "collect") not in calls and "test_step" not in epochs[-1]["info"]
+            assert calls.count(("hook", "save_best_fn")) == 1 and last == me
+        if name == "off_metric":
+            shapes = {tuple(k["shape"]) for o, m, k in log if m == "reward_metric"}
+            assert (4, 2) in shapes and len(shapes) > 1
+        if kind == "on":
+            assert all(k["sample_size"] == 0 and k["repeat"] == kw["repeat_per_collect"]
+                       and k["batch_size"] == kw["batch_size"] for k in upd)
+            assert isinstance(tr.gradient_step, float)
+        hooks = {m for o, m, _ in log if o == "hook"}
+        assert {"train_fn", "test_fn", "save_best_fn"} <= hooks | \
+            ({"test_fn"} if name == "off_no_test" else set())
+    _save("trainer_script.npz", data=np.array(json.dumps(out)))
+
+
+# --------------------------------------------------------------------------------------
+# OffpolicyTrainer over the reference Collector / VectorReplayBuffer / DQNPolicy (discrete,
+# n_step 3, eps set by train_fn / test_fn) and DDPGPolicy (n_step 1) on SynthGymEnv, whose
+# rewards and episode ends do not depend on the actions: every collect result, the counters,
+# the update calls and the loss types.  The 8 x 12-row buffer wraps during the run.
+# --------------------------------------------------------------------------------------
+def gen_offpolicy_trainer():
+    from tianshou.exploration import GaussianNoise
+    from tianshou.policy import DDPGPolicy, DQNPolicy
+    from tianshou.trainer import OffpolicyTrainer
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import Actor, Critic
+    E, ET, D, A, L = 8, 4, 8, 3, 7
+    cfg = dict(E=E, ET=ET, D=D, A=A, L=L, step_per_collect=8, step_per_epoch=64, max_epoch=2,
+               update_per_step=0.5, batch_size=16, episode_per_test=6, buffer_rows=12,
+               hidden=[16, 16], gamma=0.97, dqn_n_step=3, ddpg_n_step=1, eps_train=0.1,
+               eps_test=0.05, test_seed=9)
+
+    class DiscreteSynthGymEnv(SynthGymEnv):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            self.action_space = gym.spaces.Discrete(A)
+
+    out = dict(cfg=cfg)
+    for kind in ("dqn", "ddpg"):
+        env_cls = DiscreteSynthGymEnv if kind == "dqn" else SynthGymEnv
+        log = {"train": [], "test": [], "update_kw": [], "eps": []}
+
+        class RecCollector(Collector):
+            tag = None
+
+            def collect(self, *a, **kw):
+                res = super().collect(*a, **kw)
+                log[self.tag].append(dict(
+                    kw={k: v for k, v in kw.items() if k in ("n_step", "n_episode")},
+                    n_ep=int(res["n/ep"]), n_st=int(res["n/st"]),
+                    rews=np.asarray(res["rews"], np.float64).tolist(),
+                    lens=np.asarray(res["lens"]).astype(int).tolist(),
+                    idxs=np.asarray(res["idxs"]).astype(int).tolist(),
+                    rew=float(res["rew"]), rew_std=float(res["rew_std"]),
+                    len=float(res["len"]), len_std=float(res["len_std"]),
+                    collect_step=self.collect_step, collect_episode=self.collect_episode))
+                return res
+
+        train_envs = DummyVectorEnv([lambda e=e: env_cls(e, D, A, L) for e in range(E)])
+        test_envs = DummyVectorEnv([lambda e=e: env_cls(e, D, A, L, seed=cfg["test_seed"])
+                                    for e in range(ET)])
+        torch.manual_seed(6)
+        np.random.seed(2)
+        hooks = {}
+        if kind == "dqn":
+            net = Net(D, A, hidden_sizes=(16, 16))
+            policy = DQNPolicy(net, torch.optim.Adam(net.parameters(), lr=1e-3),
+                               discount_factor=cfg["gamma"], estimation_step=cfg["dqn_n_step"],
+                               target_update_freq=5)
+
+            def train_fn(epoch, env_step):
+                policy.set_eps(cfg["eps_train"])
+                log["eps"].append(["train", epoch, env_step])
+
+            def test_fn(epoch, env_step):
+                policy.set_eps(cfg["eps_test"])
+                log["eps"].append(["test", epoch, env_step])
+            hooks = dict(train_fn=train_fn, test_fn=test_fn)
+        else:
+            actor = Actor(Net(D, hidden_sizes=(16, 16)), (A,))
+            critic = Critic(Net(D, A, hidden_sizes=(16, 16), concat=True))
+            policy = DDPGPolicy(actor, torch.optim.Adam(actor.parameters(), lr=1e-3), critic,
+                                torch.optim.Adam(critic.parameters(), lr=1e-3), tau=0.05,
+                                gamma=cfg["gamma"], exploration_noise=GaussianNoise(sigma=0.1),
+                                estimation_step=cfg["ddpg_n_step"],
+                                action_space=train_envs.action_space[0])
+        tc = RecCollector(policy, train_envs, VectorReplayBuffer(E * cfg["buffer_rows"], E),
+                          exploration_noise=True)
+        tc.tag = "train"
+        vc = RecCollector(policy, test_envs, exploration_noise=True)
+        vc.tag = "test"
+        losses = []
+        orig_update = policy.update
+
+        def update(*a, **kw):
+            res = orig_update(*a, **kw)
+            losses.append({k: type(v).__name__ for k, v in res.items()})
+            log["update_kw"].append(dict(args=len(a), sample_size=kw["sample_size"],
+                                         buffer_is_train=kw["buffer"] is tc.buffer,
+                                         buffer_len=len(kw["buffer"])))
+            return res
+
+        policy.update = update
+        trainer = OffpolicyTrainer(policy, train_collector=tc, test_collector=vc,
+                                   max_epoch=cfg["max_epoch"],
+                                   step_per_epoch=cfg["step_per_epoch"],
+                                   step_per_collect=cfg["step_per_collect"],
+                                   update_per_step=cfg["update_per_step"],
+                                   episode_per_test=cfg["episode_per_test"],
+                                   batch_size=cfg["batch_size"], show_progress=False,
+                                   verbose=False, **hooks)
+        epochs = []
+        for epoch, stat, info in trainer:
+            epochs.append(dict(epoch=epoch, env_step=int(stat["env_step"]),
+                               gradient_step=int(stat["gradient_step"]),
+                               n_ep=int(stat["n/ep"]), n_st=int(stat["n/st"]),
+                               rew=float(stat["rew"]), len=int(stat["len"]),
+                               test_reward=float(stat["test_reward"]),
+                               best_reward=float(stat["best_reward"]),
+                               best_epoch=int(stat["best_epoch"]),
+                               loss_keys=sorted(k for k in stat if k.startswith("loss")),
+                               train_step=int(info["train_step"]),
+                               train_episode=int(info["train_episode"]),
+                               test_step=int(info["test_step"]),
+                               test_episode=int(info["test_episode"])))
+        assert trainer.gradient_step == len(losses) == 64 and trainer.env_step == 128
+        assert log["update_kw"][0]["buffer_len"] == 8 and log["update_kw"][-1]["buffer_len"] \
+            == E * cfg["buffer_rows"] < trainer.env_step  # the ring has wrapped
+        assert any(r["n_ep"] > 0 for r in log["train"])
+        out[kind] = dict(log=log, epochs=epochs, learn_types=losses,
+                         final=dict(train_collect_step=tc.collect_step,
+                                    train_collect_episode=tc.collect_episode,
+                                    test_collect_step=vc.collect_step,
+                                    test_collect_episode=vc.collect_episode,
+                                    gradient_step=trainer.gradient_step,
+                                    env_step=trainer.env_step,
+                                    best_reward=float(trainer.best_reward),
+                                    best_epoch=int(trainer.best_epoch)))
+        print(kind, "epochs", epochs, "losses", losses[0])
+    _save("offpolicy_trainer.npz", data=np.array(json.dumps(out)))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
-                             "persist", "trainer", "a2c", "dqn", "dist_dqn", "ddpg", "sac",
-                             "dsac", "redq"]
+                             "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
+                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
                  rms_wide=gen_rms_wide, rms_fullT=gen_rms_fullT,
                  stack=gen_stack, ppo_discrete=gen_ppo_discrete, npg=gen_npg, replay=gen_replay,
                  cartpole=gen_cartpole, sched=gen_sched,
-                 persist=gen_persist, trainer=gen_trainer, a2c=gen_a2c, dqn=gen_dqn,
+                 persist=gen_persist, trainer=gen_trainer, trainer_script=gen_trainer_script,
+                 offpolicy_trainer=gen_offpolicy_trainer,
+                 a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
                  redq=gen_redq)
     for w in which:
