@@ -67,6 +67,15 @@ class BasePolicy(nn.Module):
     # tsrl_replay_sample launch, no device-to-host copy before learn()); False: the generic
     # buffer.sample + compute_nstep_return path.  Both give the same bits.
     fused_sample = True
+    GRAPH_LEARN_MAX_ROWS = 65536
+
+    def _use_graph(self, batch_size: int) -> bool:
+        """``graph_learn`` of a policy that replays updates from HIP graphs.  batch_size: the
+        rows an update (on-policy: a minibatch, min(batch_size, n) -- A2C's usual batch_size
+        is "the whole batch", 99999, examples/mujoco/mujoco_a2c.py:52) can have."""
+        if self.graph_learn is None:
+            return batch_size < self.GRAPH_LEARN_MAX_ROWS
+        return bool(self.graph_learn)
 
     def __init__(self, observation_space=None, action_space=None, action_scaling: bool = False,
                  action_bound_method: Optional[Literal["clip", "tanh"]] = None,

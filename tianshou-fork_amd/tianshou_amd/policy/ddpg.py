@@ -11,16 +11,18 @@ With plain Adam / RMSprop optimisers every network's parameters, gradients and m
 flat buffers (policy/flat_adam.py, one FlatAdam per network), its target network's parameters
 are views into a second flat buffer laid out as the first, and "critic forward, loss, backward,
 optimiser pass, actor forward, critic forward, loss, backward, optimiser pass, soft update"
-replays from one captured HIP graph (``graph_learn``).
+replays from one captured HIP graph (``graph_learn``).  The target mirror, the bracket around
+each backward and the graph cache are policy/flat_learn.py's, shared with DQNPolicy.
 
 What stays on torch: a network with module buffers or another optimiser (``soft_update`` /
 ``optim.step()`` for that network; no graph replay), and ``fused = False`` -- the reference's
 op sequence on the GPU, kept as the comparison leg of tools/ddpg_update_bench.py.
 
 SACPolicy (policy/sac.py), DiscreteSACPolicy (policy/discrete_sac.py) and REDQPolicy
-(policy/redq.py) build on the same hooks.  Not built: an OffpolicyTrainer, data-parallel
-updates, a fused act kernel for deterministic actors (the Collector keeps such a policy on its
-eager device step) and reward normalisation (compute_nstep_return asserts against it).
+(policy/redq.py) build on the same hooks; OffpolicyTrainer (trainer/base.py) drives them all.
+Not built: data-parallel updates, a fused act kernel for deterministic actors (the Collector
+keeps such a policy on its eager device step) and reward normalisation (compute_nstep_return
+asserts against it).
 """
 import warnings
 from copy import deepcopy
@@ -33,7 +35,9 @@ from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
 from tianshou_amd.exploration import BaseNoise, GaussianNoise
 from tianshou_amd.policy.base import BasePolicy
-from tianshou_amd.policy.flat_adam import FlatAdam, _slot
+from tianshou_amd.policy.flat_adam import FlatAdam
+from tianshou_amd.policy.flat_learn import (f32_rows, flat_backward, mirror_target,
+                                            replay_learn_graph, target_mirrored)
 from tianshou_amd.policy.onpolicy import _is_unit_seed, _unit_seed
 from tianshou_amd.utils.capture import graph_capture
 
@@ -155,10 +159,6 @@ def neg_mean_loss(q: torch.Tensor, loss_out: Optional[torch.Tensor] = None) -> t
     return _NegMeanLoss.apply(loss_out, q)
 
 
-def _f32_rows(x, dev, n: int) -> torch.Tensor:
-    return torch.as_tensor(x, device=dev).reshape(n).to(torch.float32).contiguous()
-
-
 class DDPGPolicy(BasePolicy):
     """Constructor arguments, defaults, assertions and warnings as the reference's
     (ddpg.py:44-104).
@@ -168,7 +168,6 @@ class DDPGPolicy(BasePolicy):
     ``soft_update`` even for a plain Adam / RMSprop) and ``graph_learn`` (None / True / False:
     None replays updates of fewer than GRAPH_LEARN_MAX_ROWS rows)."""
 
-    GRAPH_LEARN_MAX_ROWS = 65536
     _critic_names: Tuple[str, ...] = ("critic",)
     # the networks with a target copy, in sync_weight's order (ddpg.py:119-120)
     _sync_order: Tuple[str, ...] = ("actor", "critic")
@@ -247,7 +246,7 @@ class DDPGPolicy(BasePolicy):
         """The flat gradient / optimiser storage of network ``name`` when its optimiser is a
         plain Adam or RMSprop over exactly its parameters (None otherwise: torch's step and
         BasePolicy.soft_update run for it).  Its target network's parameters, where it has one,
-        then become views into a second flat buffer laid out as the first."""
+        then become views into a second flat buffer (flat_learn.mirror_target)."""
         if not (self.fused and self.fused_adam and self._on_device()):
             return None
         net, old = getattr(self, name), getattr(self, name + "_old", None)
@@ -259,25 +258,13 @@ class DDPGPolicy(BasePolicy):
             st["old"] = st["src"] = None
             return None
         if old is not None and not self._old_is_flat(st, old):
-            src = fa.flat_param
-            flat_old = torch.empty_like(src)
-            o = 0
-            for p_old, p in zip(old.parameters(), fa.params):
-                v = _slot(flat_old, o, p)
-                v.copy_(p_old.detach())
-                with torch.no_grad():
-                    p_old.data = v
-                o += p.numel()
-            st["old"], st["src"] = flat_old, src
+            st["src"] = fa.flat_param
+            st["old"] = mirror_target(old, fa.params, st["src"])
         return fa
 
     @staticmethod
     def _old_is_flat(st: dict, old: torch.nn.Module) -> bool:
-        flat_old = st["old"]
-        if flat_old is None or st["src"] is not st["fa"].flat_param:
-            return False
-        lo, hi = flat_old.data_ptr(), flat_old.data_ptr() + flat_old.numel() * 4
-        return all(lo <= p.data_ptr() < hi for p in old.parameters())
+        return target_mirrored(old, st["old"], st["src"], st["fa"].flat_param)
 
     def _flat_pair(self, name: str) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         """(flat target, flat online) parameters of network ``name`` when tsrl_soft_update can
@@ -434,8 +421,8 @@ class DDPGPolicy(BasePolicy):
             weight = batch.get("weight", None)
             obs = batch.obs
             act = self._learn_act(batch, dev, n)
-            returns = _f32_rows(batch.returns, dev, n)
-            w = None if weight is None else _f32_rows(weight, dev, n)
+            returns = f32_rows(batch.returns, dev, n)
+            w = None if weight is None else f32_rows(weight, dev, n)
             draws = self._learn_draws(act)
             out = None
             if all(fa is not None for fa in fas.values()):
@@ -459,28 +446,19 @@ class DDPGPolicy(BasePolicy):
         """zero_grad, backward and optimiser step of networks ``names`` on loss ``handle``.
         Only their parameters receive gradients: the actor loss's backward runs through the
         critic without leaving anything in the critic's gradient storage."""
-        # eager: autograd hands over each gradient and one pass gathers them into the flat
-        # bucket; under graph capture it accumulates into the zeroed bucket in place
-        gather = not torch.cuda.is_current_stream_capturing()
         params = []
         for name in names:
-            fa = fas[name]
-            if fa is None:
+            if fas[name] is None:
                 getattr(self, name + "_optim").zero_grad()
-            elif gather:
-                fa.release_grads()
-            else:
-                fa.zero_grad()
             params += list(getattr(self, name).parameters())
-        torch.autograd.backward(handle, _unit_seed(handle.device), inputs=params)
+        with flat_backward([fas[name] for name in names if fas[name] is not None]):
+            torch.autograd.backward(handle, _unit_seed(handle.device), inputs=params)
         for name in names:
             fa = fas[name]
             if fa is None:
                 getattr(self, name + "_optim").step()
-                continue
-            if gather:
-                fa.gather_grads()
-            fa.clip_adam(None)  # the reference clips nothing: one optimiser pass
+            else:
+                fa.clip_adam(None)  # the reference clips nothing: one optimiser pass
 
     def _step(self, fas: Dict[str, Optional[FlatAdam]], obs, act, returns, weight,
               do_actor: bool, td_out: torch.Tensor, loss_out: torch.Tensor) -> None:
@@ -502,11 +480,6 @@ class DDPGPolicy(BasePolicy):
         self.sync_weight()
 
     # -- HIP-graph replay of one update ----------------------------------------------------------
-    def _use_graph(self, batch_size: int) -> bool:
-        if self.graph_learn is None:
-            return batch_size < self.GRAPH_LEARN_MAX_ROWS
-        return bool(self.graph_learn)
-
     def _graph_ok(self, obs, n: int) -> bool:
         if self._graph_failed or not isinstance(obs, torch.Tensor) or not obs.is_cuda:
             return False
@@ -532,36 +505,17 @@ class DDPGPolicy(BasePolicy):
         """One update replayed from a HIP graph captured once per (batch size, observation
         shape and dtype, action shape, weight present, step kind, draws, flat addresses);
         static copies of obs / act / returns / weight / the draws feed it, the losses and the
-        per-row vector come out of static outputs.  None if the capture failed (this and every
-        later update then run eagerly)."""
+        per-row vector come out of static outputs (flat_learn.replay_learn_graph).  None if the
+        capture failed (this and every later update then run eagerly)."""
         addr = self._graph_addr(fas)
-        if self._learn_graphs and next(iter(self._learn_graphs.values()))["addr"] != addr:
-            self._learn_graphs.clear()
         key = (len(returns), tuple(obs.shape), obs.dtype, tuple(act.shape), weight is not None,
                *(tuple(d.shape) for d in draws), bool(do_actor))
-        st = self._learn_graphs.get(key)
-        if st is None:
-            static = [obs.clone(), act.clone(), returns.clone(),
-                      None if weight is None else weight.clone()]
-            static_draws = [d.clone() for d in draws]
-            td = torch.empty(len(returns), dtype=torch.float32, device=act.device)
-            loss = torch.zeros(self._loss_slots(), dtype=torch.float32, device=act.device)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with self._capture(graph):
-                    self._step(fas, *static, do_actor, td, loss, *static_draws)
-            except RuntimeError as err:
-                warnings.warn(f"learn-graph capture failed, running updates eagerly: {err}")
-                self._graph_failed = True
-                self._learn_graphs.clear()
-                torch.cuda.synchronize()
-                return None
-            st = self._learn_graphs[key] = dict(addr=addr, graph=graph,
-                                                static=static + static_draws, td=td, loss=loss)
-        else:
-            for d, a in zip(st["static"], (obs, act, returns, weight, *draws)):
-                if d is not None:
-                    d.copy_(a)
-        st["graph"].replay()
-        return st["loss"], st["td"].clone()
+        out = replay_learn_graph(
+            self._learn_graphs, key, addr, (obs, act, returns, weight, *draws),
+            lambda: (torch.empty(len(returns), dtype=torch.float32, device=act.device),
+                     torch.zeros(self._loss_slots(), dtype=torch.float32, device=act.device)),
+            lambda s, td, loss: self._step(fas, *s[:4], do_actor, td, loss, *s[4:]),
+            self._capture)
+        if out is None:
+            self._graph_failed = True
+        return out

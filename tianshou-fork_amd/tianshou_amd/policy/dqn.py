@@ -10,7 +10,8 @@ as the kernels of csrc/dqn.hip: ``tsrl_dqn_target_q`` (the bootstrap value of ``
 parameters, gradients and moments live in flat buffers (policy/flat_adam.py): the optimiser
 step is one HIP pass, the target network's parameters are views into a second flat buffer
 (``sync_weight`` is one copy), and "forward, loss, backward, optimiser pass" can replay from
-a captured HIP graph (``graph_learn``).
+a captured HIP graph (``graph_learn``).  The target mirror, the bracket around the backward
+call and the per-key graph cache are policy/flat_learn.py's, shared with DDPGPolicy.
 
 What stays on torch: observations with an action mask (``obs.mask``), any other optimiser
 (``optim.step()``), and ``fused = False`` -- the reference's op sequence on the GPU, kept as
@@ -21,7 +22,6 @@ the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_
 ``_before_forward``, ``_fused_loss``) and reuse the flat storage, the sync and the graph replay
 as they are.  RainbowPolicy (NoisyLinear) is not built.
 """
-import warnings
 from copy import deepcopy
 from typing import Any, Dict, Optional, Union
 
@@ -31,7 +31,9 @@ import torch
 from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
 from tianshou_amd.policy.base import BasePolicy
-from tianshou_amd.policy.flat_adam import FlatAdam, _slot
+from tianshou_amd.policy.flat_adam import FlatAdam
+from tianshou_amd.policy.flat_learn import (f32_rows, flat_backward, mirror_target,
+                                            replay_learn_graph, target_mirrored)
 from tianshou_amd.policy.onpolicy import _is_unit_seed, _unit_seed
 from tianshou_amd.utils.capture import graph_capture
 
@@ -92,10 +94,6 @@ class _DQNLoss(torch.autograd.Function):
         return (grad_q * g_loss).to(ctx.q_dtype), None
 
 
-def _f32_rows(x, dev, n: int) -> torch.Tensor:
-    return torch.as_tensor(x, device=dev).reshape(n).to(torch.float32).contiguous()
-
-
 class DQNPolicy(BasePolicy):
     """Constructor arguments, defaults and assertions as the reference's (dqn.py:41-69).
 
@@ -103,8 +101,6 @@ class DQNPolicy(BasePolicy):
     formulation throughout), ``fused_adam`` (False: keep ``optim.step()`` even for a plain
     Adam / RMSprop) and ``graph_learn`` (None / True / False, read as on A2CPolicy /
     PPOPolicy: None replays updates of fewer than GRAPH_LEARN_MAX_ROWS rows)."""
-
-    GRAPH_LEARN_MAX_ROWS = 65536
 
     def __init__(self, model: torch.nn.Module, optim: torch.optim.Optimizer,
                  discount_factor: float = 0.99, estimation_step: int = 1,
@@ -134,6 +130,7 @@ class DQNPolicy(BasePolicy):
         self._learn_graphs: Dict[Any, dict] = {}
         self._flat: Optional[FlatAdam] = None
         self._old_flat: Optional[torch.Tensor] = None
+        self._old_src: Optional[torch.Tensor] = None  # the flat_param _old_flat mirrors
         self._warm = False
 
     def set_eps(self, eps: float) -> None:
@@ -154,7 +151,7 @@ class DQNPolicy(BasePolicy):
         """The flat gradient / optimiser storage of the Q-network when the optimiser is a plain
         Adam or RMSprop over exactly its parameters (None otherwise: torch's step runs).  The
         target network's parameters then become views into a second flat buffer laid out as
-        the first."""
+        the first (flat_learn.mirror_target)."""
         if not (self.fused and self.fused_adam and self._on_device()):
             return None
         fa = self._flat
@@ -164,25 +161,12 @@ class DQNPolicy(BasePolicy):
             self._old_flat = None
             return None
         if self._target and not self._old_is_flat(fa):
-            src = fa.flat_param
-            old = torch.empty_like(src)
-            o = 0
-            for p_old, p in zip(self.model_old.parameters(), fa.params):
-                v = _slot(old, o, p)
-                v.copy_(p_old.detach())
-                with torch.no_grad():
-                    p_old.data = v
-                o += p.numel()
-            self._old_flat = old
-            self._old_src = src
+            self._old_src = fa.flat_param
+            self._old_flat = mirror_target(self.model_old, fa.params, self._old_src)
         return fa
 
     def _old_is_flat(self, fa: FlatAdam) -> bool:
-        old = self._old_flat
-        if old is None or self._old_src is not fa.flat_param:
-            return False
-        lo, hi = old.data_ptr(), old.data_ptr() + old.numel() * 4
-        return all(lo <= p.data_ptr() < hi for p in self.model_old.parameters())
+        return target_mirrored(self.model_old, self._old_flat, self._old_src, fa.flat_param)
 
     def sync_weight(self) -> None:
         """dqn.py:81-83.  With the flat storage bound and no module buffers (BatchNorm
@@ -349,10 +333,10 @@ class DQNPolicy(BasePolicy):
         return ()
 
     def _returns_rows(self, batch: Batch, dev, n: int) -> torch.Tensor:
-        return _f32_rows(batch.returns, dev, n)
+        return f32_rows(batch.returns, dev, n)
 
     def _loss_weight(self, weight, dev, n: int) -> Optional[torch.Tensor]:
-        return None if weight is None or self._clip_loss_grad else _f32_rows(weight, dev, n)
+        return None if weight is None or self._clip_loss_grad else f32_rows(weight, dev, n)
 
     def _before_forward(self, info, *extra):
         """No-grad work on the extra inputs ahead of the forward on obs; its result reaches
@@ -374,25 +358,12 @@ class DQNPolicy(BasePolicy):
             loss.backward()
             self.optim.step()
             return loss.detach(), td
-        # eager: autograd hands over each gradient and one pass gathers them into the flat
-        # bucket; under graph capture it accumulates into the zeroed bucket in place
-        gather = not torch.cuda.is_current_stream_capturing()
-        if gather:
-            fa.release_grads()
-        else:
-            fa.zero_grad()
-        loss.backward(_unit_seed(loss.device))
-        if gather:
-            fa.gather_grads()
+        with flat_backward((fa,)):
+            loss.backward(_unit_seed(loss.device))
         fa.clip_adam(None)  # the reference clips nothing: one optimiser pass
         return loss.detach(), td
 
     # -- HIP-graph replay of one update ----------------------------------------------------------
-    def _use_graph(self, batch_size: int) -> bool:
-        if self.graph_learn is None:
-            return batch_size < self.GRAPH_LEARN_MAX_ROWS
-        return bool(self.graph_learn)
-
     def _graph_ok(self, obs, n: int) -> bool:
         """Unmasked device observations, no earlier capture failure, and -- as in
         FusedLearnMixin._learn_cat -- conv trunks only with graph_learn=True."""
@@ -408,36 +379,18 @@ class DQNPolicy(BasePolicy):
         """One update's forward, loss, backward and flat optimiser pass replayed from a HIP
         graph captured once per (batch size, observation shape and dtype, flat addresses);
         static copies of obs / act / returns / weight (and a subclass's extra inputs) feed it,
-        the loss and the TD errors come out of static outputs.  None if the capture failed
-        (this and every later update then run eagerly)."""
+        the loss and the TD errors come out of static outputs (flat_learn.replay_learn_graph).
+        None if the capture failed (this and every later update then run eagerly)."""
         fa.bind_grads()
         addr = (fa.flat_grad.data_ptr(), tuple(p.data_ptr() for p in fa.params))
-        if self._learn_graphs and next(iter(self._learn_graphs.values()))["addr"] != addr:
-            self._learn_graphs.clear()
         key = (len(act), tuple(obs.shape), obs.dtype, weight is not None,
                tuple((tuple(e.shape), e.dtype) for e in extra))
-        st = self._learn_graphs.get(key)
-        if st is None:
-            static = [obs.clone(), act.clone(), returns.clone(),
-                      None if weight is None else weight.clone(), *(e.clone() for e in extra)]
-            td = torch.empty(len(act), dtype=torch.float32, device=act.device)
-            loss = torch.empty((), dtype=torch.float32, device=act.device)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with self._capture(graph):
-                    self._step(fa, static[0], Batch(), *static[1:], td_out=td, loss_out=loss)
-            except RuntimeError as err:
-                warnings.warn(f"learn-graph capture failed, running updates eagerly: {err}")
-                self._graph_failed = True
-                self._learn_graphs.clear()
-                torch.cuda.synchronize()
-                return None
-            st = self._learn_graphs[key] = dict(addr=addr, graph=graph, static=static, td=td,
-                                                loss=loss)
-        else:
-            for d, a in zip(st["static"], (obs, act, returns, weight, *extra)):
-                if d is not None:
-                    d.copy_(a)
-        st["graph"].replay()
-        return st["loss"], st["td"].clone()
+        out = replay_learn_graph(
+            self._learn_graphs, key, addr, (obs, act, returns, weight, *extra),
+            lambda: (torch.empty(len(act), dtype=torch.float32, device=act.device),
+                     torch.empty((), dtype=torch.float32, device=act.device)),
+            lambda s, td, loss: self._step(fa, s[0], Batch(), *s[1:], td_out=td, loss_out=loss),
+            self._capture)
+        if out is None:
+            self._graph_failed = True
+        return out

@@ -27,6 +27,7 @@ from tianshou_amd.data.batch import Batch, gather_rows
 from tianshou_amd.dist import LOG
 from tianshou_amd.utils.capture import graph_capture
 from tianshou_amd.policy.flat_adam import FlatAdam
+from tianshou_amd.policy.flat_learn import flat_backward
 from tianshou_amd.utils.np_perm import LegacyPermutation
 
 # a shared uint8 conv trunk reads each minibatch's frame stacks in place from the whole batch
@@ -492,16 +493,7 @@ class FusedLearnMixin:
             nn.utils.clip_grad_norm_(self._actor_critic.parameters(), max_norm=self._grad_norm)
         self.optim.step()
 
-    # -- HIP-graph replay of whole epochs ------------------------------------------------------
-    GRAPH_LEARN_MAX_ROWS = 65536
-
-    def _use_graph(self, batch_size: int) -> bool:
-        """batch_size: the rows a minibatch can have, min(batch_size, n) -- A2C's usual
-        batch_size is "the whole batch" (99999, examples/mujoco/mujoco_a2c.py:52)."""
-        if self.graph_learn is None:
-            return batch_size < self.GRAPH_LEARN_MAX_ROWS
-        return bool(self.graph_learn)
-
+    # -- HIP-graph replay of whole epochs (BasePolicy._use_graph reads graph_learn) ------------
     def _graph_ready(self, chunks) -> bool:
         """An epoch of fused minibatches can be captured once and replayed: a static plan
         (single process, or data parallel with per-rank splits and a capturable backend --
@@ -668,16 +660,8 @@ class FusedLearnMixin:
         loss, t = _CatPPOLoss.apply(x, value, (*arrays, idx, self._params(b_glob), self.dp,
                                                self._cat))
         if fa is not None:
-            # eager: autograd hands over each gradient and one pass gathers them into the flat
-            # bucket; under graph capture it accumulates into the zeroed bucket in place
-            gather = loss.is_cuda and not torch.cuda.is_current_stream_capturing()
-            if gather:
-                fa.release_grads()
-            else:
-                fa.zero_grad()
-            loss.backward(_unit_seed(loss.device))
-            if gather:
-                fa.gather_grads()
+            with flat_backward((fa,), eager=loss.is_cuda):
+                loss.backward(_unit_seed(loss.device))
             self.dp.all_reduce_(fa.flat_grad, kind="grad")
             fa.clip_adam(self._grad_norm, scale_grads=last)
             return t

@@ -26,8 +26,7 @@ returns a 1-tuple because of a stray comma (redq.py:195).  ``fused = False`` is 
 op sequence, the comparison leg and the CPU path.
 
 Not built: evaluating only the sampled subset of target critics, fusing the ensemble's H -> 1
-head with the loss, a hand-written ensemble GEMM, an OffpolicyTrainer, data-parallel REDQ and a
-fused collect step.
+head with the loss, a hand-written ensemble GEMM, data-parallel REDQ and a fused collect step.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union

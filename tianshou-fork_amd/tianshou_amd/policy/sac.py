@@ -21,8 +21,8 @@ validates as the reference does), and ``batch.weight`` and the actions are f32 d
 ``fused = False`` is the reference's op sequence, the comparison leg and the CPU path.
 
 DiscreteSACPolicy (policy/discrete_sac.py) subclasses this class; REDQPolicy (policy/redq.py)
-shares _SquashedGaussianMixin with it.  Not built: an OffpolicyTrainer and data-parallel
-updates.
+shares _SquashedGaussianMixin with it; OffpolicyTrainer (trainer/base.py) drives all three.
+Not built: data-parallel updates.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union
