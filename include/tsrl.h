@@ -896,6 +896,59 @@ int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* ret
                          double* partials, float* loss, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * RainbowPolicy (tianshou/policy/modelfree/rainbow.py): NoisyLinear (utils/net/discrete.py:
+ * 319-394) and the dueling combine (utils/net/common.py:276-284), csrc/noisy.hip.  All tensors
+ * f32 and 4-byte aligned unless noted; no call synchronises or allocates, so each can be
+ * captured into a graph.  No product or sum of the three noisy calls is contracted into an FMA.
+ * tsrl_noisy_eps: out[i] = sign(x[i]) * sqrt(|x[i]|) over n values (discrete.py:361-363 after
+ *   its randn), sign(+-0) = sign(NaN) = 0, the square root correctly rounded: torch's
+ *   x.sign().mul_(x.abs().sqrt_()) bit for bit.  One launch; n == 0 launches nothing.
+ * tsrl_noisy_weights: for each of the n_layers descriptors of `table` (DEVICE memory, read by
+ *   the kernel): w_eff[o][i] = fl(mu_w[o][i] + fl(sigma_w[o][i] * fl(eps_q[o] * eps_p[i]))) and
+ *   b_eff[o] = fl(mu_b[o] + fl(sigma_b[o] * eps_q[o])), row-major [out, in]: torch's
+ *   mu_W + sigma_W * eps_q.ger(eps_p) bit for bit (discrete.py:371-374).  One launch for the
+ *   whole table, grid row y = layer y; max_elems = the largest in * out of the table (it sizes
+ *   the grid).  A layer whose mu_w, sigma_w and w_eff are 16-byte aligned and whose `in` is a
+ *   multiple of 4 moves 16 bytes per lane, any other 4.  n_layers == 0 launches nothing.
+ * tsrl_noisy_grads: one layer's backward: g_sigma_w[o][i] = fl(gw[o][i] * fl(eps_q[o] *
+ *   eps_p[i])), g_sigma_b[o] = fl(gb[o] * eps_q[o]) for gw [out, in] and gb [out], the
+ *   gradients of w_eff and b_eff (which are the gradients of mu_w and mu_b as they stand):
+ *   autograd's gradients of the formulation above bit for bit.  16-byte accesses under the
+ *   same rule on gw and g_sigma_w.  in == 0 or out == 0 launches nothing.
+ * tsrl_dueling_fwd: out[r][a][k] = q[r][a][k] - mean_a' q[r][a'][k] + v[r][k] for q [b,
+ *   num_actions, n] and v [b, n]; with softmax != 0 followed by a softmax over k.  One
+ *   workgroup per row r, the row in LDS, f64 arithmetic on the f32 inputs, rounded once.
+ * tsrl_dueling_bwd: from g_out and the saved out (read with softmax != 0 only): g_l = out *
+ *   (g_out - sum_k g_out * out) with softmax, else g_out; g_v[r][k] = sum_a g_l[r][a][k];
+ *   g_q[r][a][k] = g_l[r][a][k] - (1 / num_actions) sum_a' g_l[r][a'][k].
+ * Both dueling calls: num_actions * n <= TSRL_DUELING_MAX_ROW, else they launch nothing and
+ *   return TSRL_ERR_DUELING_ROW (no hipError value); b == 0 launches nothing.
+ * ------------------------------------------------------------------------------- */
+#define TSRL_DUELING_MAX_ROW 4096
+#define TSRL_ERR_DUELING_ROW 100001
+typedef struct tsrl_noisy_layer {
+    const float* mu_w;
+    const float* sigma_w;
+    const float* mu_b;
+    const float* sigma_b;
+    const float* eps_p; /* [in] */
+    const float* eps_q; /* [out] */
+    float* w_eff;       /* [out, in] */
+    float* b_eff;       /* [out] */
+    int64_t in;
+    int64_t out;
+} tsrl_noisy_layer;
+int tsrl_noisy_eps(const float* x, int64_t n, float* out, void* stream);
+int tsrl_noisy_weights(const tsrl_noisy_layer* table, int64_t n_layers, int64_t max_elems,
+                       void* stream);
+int tsrl_noisy_grads(const float* gw, const float* gb, const float* eps_p, const float* eps_q,
+                     int64_t in, int64_t out, float* g_sigma_w, float* g_sigma_b, void* stream);
+int tsrl_dueling_fwd(const float* q, const float* v, int64_t b, int64_t num_actions, int64_t n,
+                     int softmax, float* out, void* stream);
+int tsrl_dueling_bwd(const float* g_out, const float* out, int64_t b, int64_t num_actions,
+                     int64_t n, int softmax, float* g_q, float* g_v, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * DDPGPolicy / TD3Policy (tianshou/policy/modelfree/ddpg.py, td3.py), csrc/ddpg.hip.  Every
  * call is one launch unless noted; all tensors f32 unless noted.
  * tsrl_soft_update: sync_weight (ddpg.py:117-120, td3.py:93-96) over up to four (target,

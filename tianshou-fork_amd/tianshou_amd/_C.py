@@ -235,6 +235,11 @@ _SIGS = {
                                _p, _p], ctypes.c_int),
     "tsrl_qr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
                              ctypes.c_int),
+    "tsrl_noisy_eps": ([_p, _i64, _p, _p], ctypes.c_int),
+    "tsrl_noisy_weights": ([_p, _i64, _i64, _p], ctypes.c_int),
+    "tsrl_noisy_grads": ([_p, _p, _p, _p, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_dueling_fwd": ([_p, _p, _i64, _i64, _i64, ctypes.c_int, _p, _p], ctypes.c_int),
+    "tsrl_dueling_bwd": ([_p, _p, _i64, _i64, _i64, ctypes.c_int, _p, _p, _p], ctypes.c_int),
     "tsrl_soft_update": ([_p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _d, _p],
                          ctypes.c_int),
     "tsrl_td3_smooth": ([_p, _p, _d, _d, _i64, _p, _p], ctypes.c_int),
@@ -257,6 +262,12 @@ _SIGS = {
     "tsrl_redq_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p, _p],
                                      ctypes.c_int),
 }
+
+# tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
+# ``tsrl_noisy_layer``'s eight pointers, then in and out (all fields are 8 bytes wide)
+NOISY_DESC_WORDS = 10
+DUELING_MAX_ROW = 4096        # TSRL_DUELING_MAX_ROW
+ERR_DUELING_ROW = 100001      # TSRL_ERR_DUELING_ROW
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

@@ -7,6 +7,7 @@ from tianshou_amd.policy.trpo import TRPOPolicy
 from tianshou_amd.policy.dqn import DQNPolicy
 from tianshou_amd.policy.c51 import C51Policy
 from tianshou_amd.policy.qrdqn import QRDQNPolicy
+from tianshou_amd.policy.rainbow import RainbowPolicy
 from tianshou_amd.policy.ddpg import DDPGPolicy
 from tianshou_amd.policy.td3 import TD3Policy
 from tianshou_amd.policy.sac import SACPolicy
@@ -14,5 +15,5 @@ from tianshou_amd.policy.discrete_sac import DiscreteSACPolicy
 from tianshou_amd.policy.redq import REDQPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
-           "DQNPolicy", "C51Policy", "QRDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy",
-           "DiscreteSACPolicy", "REDQPolicy"]
+           "DQNPolicy", "C51Policy", "QRDQNPolicy", "RainbowPolicy", "DDPGPolicy", "TD3Policy",
+           "SACPolicy", "DiscreteSACPolicy", "REDQPolicy"]

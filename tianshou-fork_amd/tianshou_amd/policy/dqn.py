@@ -20,7 +20,7 @@ the comparison leg of tools/dqn_update_bench.py.
 The distributional subclasses C51Policy (policy/c51.py) and QRDQNPolicy (policy/qrdqn.py) fill
 the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_weight``,
 ``_before_forward``, ``_fused_loss``) and reuse the flat storage, the sync and the graph replay
-as they are.  RainbowPolicy (NoisyLinear) is not built.
+as they are; RainbowPolicy (policy/rainbow.py) is C51Policy over NoisyLinear layers.
 """
 from copy import deepcopy
 from typing import Any, Dict, Optional, Union
@@ -375,6 +375,10 @@ class DQNPolicy(BasePolicy):
         """The capture context of a learn graph (utils.capture.graph_capture)."""
         return graph_capture(graph)
 
+    def _graph_addrs(self) -> tuple:
+        """Further addresses a subclass's captured update is tied to."""
+        return ()
+
     def _graph_step(self, fa: FlatAdam, obs, act, returns, weight, *extra):
         """One update's forward, loss, backward and flat optimiser pass replayed from a HIP
         graph captured once per (batch size, observation shape and dtype, flat addresses);
@@ -382,7 +386,8 @@ class DQNPolicy(BasePolicy):
         the loss and the TD errors come out of static outputs (flat_learn.replay_learn_graph).
         None if the capture failed (this and every later update then run eagerly)."""
         fa.bind_grads()
-        addr = (fa.flat_grad.data_ptr(), tuple(p.data_ptr() for p in fa.params))
+        addr = (fa.flat_grad.data_ptr(), tuple(p.data_ptr() for p in fa.params)) + \
+            self._graph_addrs()
         key = (len(act), tuple(obs.shape), obs.dtype, weight is not None,
                tuple((tuple(e.shape), e.dtype) for e in extra))
         out = replay_learn_graph(

@@ -1,6 +1,9 @@
 """Actor/critic networks with the reference's module layout, so ``state_dict()`` keys match
 tianshou 0.5.1 checkpoints (utils/net/common.py:56-285, continuous.py:87-235,
-discrete.py:12-121).  The GEMMs run through PyTorch-ROCm (hipBLASLt) on the GPU."""
+discrete.py:12-121, 319-394).  The GEMMs run through PyTorch-ROCm (hipBLASLt) on the GPU;
+NoisyLinear's effective parameters, its sigma gradients and the dueling combine are the kernels
+of csrc/noisy.hip."""
+import contextlib
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
 
 import numpy as np
@@ -52,30 +55,38 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
-        gx = gw = gb = None
-        if torch.is_grad_enabled():
-            # backward of a create_graph pass (NPG/TRPO's KL Hessian-vector products): only
-            # differentiable torch ops, so the double backward sees the whole graph
-            if ctx.needs_input_grad[0]:
-                gx = gy @ weight
-            if ctx.needs_input_grad[1]:
-                gw = gy.t() @ x
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                gb = gy.sum(0)
-            return gx, gw, gb
-        if ctx.needs_input_grad[0]:
+        need_x, need_w = ctx.needs_input_grad[:2]
+        return _linear_grads(x, weight, gy, need_x, need_w,
+                             ctx.has_bias and ctx.needs_input_grad[2])
+
+
+def _linear_grads(x, weight, gy, need_x: bool, need_w: bool, need_b: bool):
+    """(gx, gw, gb) of y = x W^T + b from gy; an entry not needed is None.  _LinearFn's
+    backward, shared with NoisyLinear's."""
+    gx = gw = gb = None
+    if torch.is_grad_enabled():
+        # backward of a create_graph pass (NPG/TRPO's KL Hessian-vector products): only
+        # differentiable torch ops, so the double backward sees the whole graph
+        if need_x:
             gx = gy @ weight
-        if ctx.needs_input_grad[1]:
-            s = _split_factor(x.shape[0])
-            if s > 1 and x.is_cuda:
-                part = torch.bmm(gy.reshape(s, -1, gy.shape[1]).transpose(1, 2),
-                                 x.reshape(s, -1, x.shape[1]))
-                gw = sum_rows(part.reshape(s, -1)).view_as(weight)
-            else:
-                gw = gy.t() @ x
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = sum_rows(gy) if gy.is_cuda else gy.sum(0)
+        if need_w:
+            gw = gy.t() @ x
+        if need_b:
+            gb = gy.sum(0)
         return gx, gw, gb
+    if need_x:
+        gx = gy @ weight
+    if need_w:
+        s = _split_factor(x.shape[0])
+        if s > 1 and x.is_cuda:
+            part = torch.bmm(gy.reshape(s, -1, gy.shape[1]).transpose(1, 2),
+                             x.reshape(s, -1, x.shape[1]))
+            gw = sum_rows(part.reshape(s, -1)).view_as(weight)
+        else:
+            gw = gy.t() @ x
+    if need_b:
+        gb = sum_rows(gy) if gy.is_cuda else gy.sum(0)
+    return gx, gw, gb
 
 
 class Linear(nn.Linear):
@@ -111,6 +122,298 @@ class EnsembleLinear(nn.Module):
         if self.bias is not None:
             x = x + self.bias
         return x
+
+
+# -- NoisyLinear (utils/net/discrete.py:319-394) ---------------------------------------------------
+# The effective parameters W_eff = mu_W + sigma_W * outer(eps_q, eps_p) and b_eff of every fused
+# training-mode layer on the GPU are built by ONE tsrl_noisy_weights launch per group of
+# networks (refresh_noisy) instead of three torch launches per layer and forward.  A layer trusts
+# its W_eff only inside a ``noisy_hold`` scope whose entry built it AND while the data pointers
+# and ``_version`` counters of its six tensors are the ones seen then.  Outside a scope nothing
+# is trusted: a write through ``p.data`` or through a raw pointer (the flat optimiser pass,
+# tsrl_noisy_eps, the flat target copy) bumps no counter, so every scope entry from outside
+# rebuilds.  Net.forward and net_atari.Rainbow.forward open a scope around their layers (one
+# launch per forward); RainbowPolicy opens one around the three forwards of an update (one
+# launch per update, the first node of the learn graph).
+_hold_depth = 0
+_NOISY_TABLES: Dict[tuple, torch.Tensor] = {}  # descriptor tables by addresses and sizes
+
+
+class _NoisyLinearFn(torch.autograd.Function):
+    """y = x W_eff^T + b_eff over the layer's cached effective parameters.  The backward is
+    _LinearFn's (gx, the split-K gW, gb); the gradients of mu_W / mu_bias are gW / gb as they
+    stand, those of sigma_W / sigma_bias one tsrl_noisy_grads launch."""
+
+    @staticmethod
+    def forward(ctx, x, mu_W, sigma_W, mu_bias, sigma_bias, layer):
+        w, b = layer._W_eff, layer._b_eff
+        ctx.save_for_backward(x, w, layer.eps_p, layer.eps_q)
+        return torch.addmm(b, x, w.t())
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, eps_p, eps_q = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        fused = not torch.is_grad_enabled() and all(need[1:5])
+        gx, gw, gb = _linear_grads(x, w, gy, need[0], need[1] or need[2], need[3] or need[4])
+        if not fused:  # a create_graph pass, or frozen parameters: differentiable torch ops
+            gsw = gw * eps_q.ger(eps_p) if need[2] else None
+            gsb = gb * eps_q if need[4] else None
+            return gx, gw if need[1] else None, gsw, gb if need[3] else None, gsb, None
+        gw, gb = gw.contiguous(), gb.contiguous()
+        gsw, gsb = torch.empty_like(gw), torch.empty_like(gb)
+        out_f, in_f = gw.shape
+        _C.check(_C.lib().tsrl_noisy_grads(
+            _C.ptr(gw), _C.ptr(gb), _C.ptr(eps_p), _C.ptr(eps_q), in_f, out_f, _C.ptr(gsw),
+            _C.ptr(gsb), _C.stream_ptr(gw.device)), "tsrl_noisy_grads")
+        return gx, gw, gsw, gb, gsb, None
+
+
+class NoisyLinear(nn.Module):
+    """Noisy Networks' factorised-noise linear layer, arXiv:1706.10295 (discrete.py:319-379):
+    the reference's parameter and buffer names, ``reset()`` / ``sample()`` draw order and
+    ``state_dict()``.  In eval mode the forward uses ``mu_W`` / ``mu_bias`` alone.  In training
+    mode on the GPU it runs over the cached effective parameters (see above; they are plain
+    attributes, never part of ``state_dict()``, and a ``deepcopy`` gets its own); on CPU
+    tensors, or with ``fused = False``, it is the reference's formulation on torch."""
+
+    fused = True
+
+    def __init__(self, in_features: int, out_features: int, noisy_std: float = 0.5) -> None:
+        super().__init__()
+        self.mu_W = nn.Parameter(torch.empty(out_features, in_features))
+        self.sigma_W = nn.Parameter(torch.empty(out_features, in_features))
+        self.mu_bias = nn.Parameter(torch.empty(out_features))
+        self.sigma_bias = nn.Parameter(torch.empty(out_features))
+        self.register_buffer("eps_p", torch.empty(in_features))
+        self.register_buffer("eps_q", torch.empty(out_features))
+        self.in_features = in_features
+        self.out_features = out_features
+        self.sigma = noisy_std
+        self._W_eff: Optional[torch.Tensor] = None
+        self._b_eff: Optional[torch.Tensor] = None
+        self._fresh_key = None
+        self.reset()
+        self.sample()
+
+    def reset(self) -> None:
+        bound = 1 / np.sqrt(self.in_features)
+        self.mu_W.data.uniform_(-bound, bound)
+        self.mu_bias.data.uniform_(-bound, bound)
+        self.sigma_W.data.fill_(self.sigma / np.sqrt(self.in_features))
+        self.sigma_bias.data.fill_(self.sigma / np.sqrt(self.in_features))
+
+    def f(self, x: torch.Tensor) -> torch.Tensor:
+        x = torch.randn(x.size(0), device=x.device)
+        return x.sign().mul_(x.abs().sqrt_())
+
+    def sample(self) -> None:
+        self.eps_p.copy_(self.f(self.eps_p))
+        self.eps_q.copy_(self.f(self.eps_q))
+
+    # -- the effective-parameter cache ------------------------------------------------------------
+    def _cacheable(self) -> bool:
+        return self.training and self.fused and self.mu_W.is_cuda
+
+    def _tensors(self):
+        return (self.mu_W, self.sigma_W, self.mu_bias, self.sigma_bias, self.eps_p, self.eps_q)
+
+    def _state_key(self) -> tuple:
+        return tuple((t.data_ptr(), t._version) for t in self._tensors()) + \
+            (self._W_eff.data_ptr(), self._b_eff.data_ptr())
+
+    def _is_fresh(self) -> bool:
+        return self._W_eff is not None and self._fresh_key == self._state_key()
+
+    def _descriptor(self) -> tuple:
+        """The layer's tsrl_noisy_layer words; allocates W_eff / b_eff where the parameters
+        live."""
+        w = self._W_eff
+        if w is None or w.device != self.mu_W.device or w.shape != self.mu_W.shape:
+            self._W_eff = torch.empty(self.mu_W.shape, dtype=torch.float32,
+                                      device=self.mu_W.device)
+            self._b_eff = torch.empty(self.mu_bias.shape, dtype=torch.float32,
+                                      device=self.mu_W.device)
+            self._fresh_key = None
+        return tuple(_C.ptr(t.detach(), torch.float32) for t in self._tensors()) + \
+            (self._W_eff.data_ptr(), self._b_eff.data_ptr(), self.in_features, self.out_features)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.training:
+            return torch.nn.functional.linear(x, self.mu_W, self.mu_bias)
+        if not (self.fused and x.is_cuda and self.mu_W.is_cuda and x.dtype == torch.float32):
+            weight = self.mu_W + self.sigma_W * self.eps_q.ger(self.eps_p)
+            bias = self.mu_bias + self.sigma_bias * self.eps_q.clone()
+            return torch.nn.functional.linear(x, weight, bias)
+        if not (_hold_depth and self._is_fresh()):
+            refresh_noisy(self)
+        if x.dim() == 2:
+            return _NoisyLinearFn.apply(x, self.mu_W, self.sigma_W, self.mu_bias,
+                                        self.sigma_bias, self)
+        y = _NoisyLinearFn.apply(x.reshape(-1, self.in_features), self.mu_W, self.sigma_W,
+                                 self.mu_bias, self.sigma_bias, self)
+        return y.view(*x.shape[:-1], self.out_features)
+
+
+def noisy_layers(*models: nn.Module) -> list:
+    return [m for model in models for m in model.modules() if isinstance(m, NoisyLinear)]
+
+
+def _noisy_table(layers) -> Tuple[torch.Tensor, int, tuple]:
+    """(device descriptor table, largest in * out, key) of ``layers``, the table cached by its
+    key: the device and the addresses and sizes it holds (it is static device memory: a
+    captured launch reads it at every replay, so an entry is never dropped)."""
+    dev = layers[0].mu_W.device
+    key = (dev.index,) + tuple(m._descriptor() for m in layers)
+    table = _NOISY_TABLES.get(key)
+    if table is None:
+        table = _NOISY_TABLES[key] = torch.tensor(key[1:], dtype=torch.int64).to(dev)
+    return table, max(m.in_features * m.out_features for m in layers), key
+
+
+def prepare_noisy(*models: nn.Module) -> tuple:
+    """Allocate what refresh_noisy(*models) needs (effective parameters, descriptor table), so
+    that a later call can be captured into a graph; returns the table's key."""
+    layers = [m for m in noisy_layers(*models) if m._cacheable()]
+    return _noisy_table(layers)[2] if layers else ()
+
+
+def _refresh_layers(layers) -> None:
+    table, max_elems, _ = _noisy_table(layers)
+    _C.check(_C.lib().tsrl_noisy_weights(_C.ptr(table), len(layers), max_elems,
+                                         _C.stream_ptr(table.device)), "tsrl_noisy_weights")
+    for m in layers:
+        m._fresh_key = m._state_key()
+
+
+def refresh_noisy(*models: nn.Module) -> bool:
+    """Build W_eff / b_eff of every fused training-mode NoisyLinear on the GPU under ``models``
+    from the current parameters and noise: one tsrl_noisy_weights launch.  False if there is
+    no such layer."""
+    layers = [m for m in noisy_layers(*models) if m._cacheable()]
+    if layers:
+        _refresh_layers(layers)
+    return bool(layers)
+
+
+@contextlib.contextmanager
+def noisy_hold(*models: nn.Module):
+    """Inside the scope the NoisyLinear layers of ``models`` compute with the effective
+    parameters built at its entry (entered from outside any scope: always rebuilt; nested: only
+    if a layer's tensors moved or changed version since)."""
+    global _hold_depth
+    layers = [m for m in noisy_layers(*models) if m._cacheable()]
+    if layers and not (_hold_depth and all(m._is_fresh() for m in layers)):
+        _refresh_layers(layers)
+    _hold_depth += 1
+    try:
+        yield
+    finally:
+        _hold_depth -= 1
+
+
+def _eps_flat(model: nn.Module, layers) -> torch.Tensor:
+    """One flat buffer that every eps_p / eps_q of ``layers`` is a view of, in sample order
+    (made on first use, and again if a buffer was moved out of it)."""
+    flat = model.__dict__.get("_noisy_eps_flat")
+    o, ok = 0, flat is not None and flat.device == layers[0].eps_p.device
+    for m in layers:
+        for t in (m.eps_p, m.eps_q):
+            ok = ok and o + t.numel() <= flat.numel() and \
+                t.data_ptr() == flat.data_ptr() + 4 * o
+            o += t.numel()
+    if ok and o == flat.numel():
+        return flat
+    flat = torch.empty(o, dtype=torch.float32, device=layers[0].eps_p.device)
+    o = 0
+    for m in layers:
+        for t in (m.eps_p, m.eps_q):
+            v = flat[o:o + t.numel()]
+            v.copy_(t)
+            t.data = v
+            o += t.numel()
+    model.__dict__["_noisy_eps_flat"] = flat
+    return flat
+
+
+def sample_noise(model: nn.Module) -> bool:
+    """discrete.py:382-394: resample every NoisyLinear under ``model``; True if there is one.
+    On the GPU (all layers fused and on one device) the reference's ``torch.randn`` calls are
+    made in its order and sizes into slices of one staging buffer and ONE tsrl_noisy_eps
+    launch writes every eps_p / eps_q, which keep their addresses: a seeded run yields the
+    reference's values, and a captured update reads the fresh noise."""
+    layers = noisy_layers(model)
+    if not layers:
+        return False
+    dev = layers[0].eps_p.device
+    if dev.type != "cuda" or not all(m.fused and m.eps_p.device == dev and
+                                     m.eps_q.device == dev for m in layers):
+        for m in layers:
+            m.sample()
+        return True
+    flat = _eps_flat(model, layers)
+    stage = torch.empty_like(flat)
+    o = 0
+    for m in layers:
+        for n in (m.in_features, m.out_features):
+            torch.randn(n, device=dev, out=stage[o:o + n])
+            o += n
+    _C.check(_C.lib().tsrl_noisy_eps(_C.ptr(stage), o, _C.ptr(flat), _C.stream_ptr(dev)),
+             "tsrl_noisy_eps")
+    return True
+
+
+# -- the dueling combine (utils/net/common.py:276-284) ---------------------------------------------
+class _DuelingRowTooLarge(Exception):
+    pass
+
+
+class _DuelingFn(torch.autograd.Function):
+    """out = q - q.mean(1, keepdim) + v (and a softmax over the last dimension) for q
+    [b, A, N] and v [b, N] as tsrl_dueling_fwd / tsrl_dueling_bwd."""
+
+    @staticmethod
+    def forward(ctx, q, v, softmax):
+        qc, vc = q.detach().float().contiguous(), v.detach().float().contiguous()
+        b, A, N = qc.shape
+        out = torch.empty_like(qc)
+        rc = _C.lib().tsrl_dueling_fwd(_C.ptr(qc), _C.ptr(vc), b, A, N, int(softmax), _C.ptr(out),
+                                       _C.stream_ptr(qc.device))
+        if rc == _C.ERR_DUELING_ROW:
+            raise _DuelingRowTooLarge
+        _C.check(rc, "tsrl_dueling_fwd")
+        ctx.softmax = int(softmax)
+        ctx.v_shape = v.shape
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        (out,) = ctx.saved_tensors
+        b, A, N = out.shape
+        g = g_out.float().contiguous()
+        g_q = torch.empty_like(out)
+        g_v = torch.empty(b, N, dtype=torch.float32, device=out.device)
+        _C.check(_C.lib().tsrl_dueling_bwd(_C.ptr(g), _C.ptr(out), b, A, N, ctx.softmax,
+                                           _C.ptr(g_q), _C.ptr(g_v), _C.stream_ptr(out.device)),
+                 "tsrl_dueling_bwd")
+        return g_q, g_v.view(ctx.v_shape), None
+
+
+def dueling_combine(q: torch.Tensor, v: torch.Tensor, softmax: bool,
+                    fused: bool = True) -> torch.Tensor:
+    """q - q.mean(dim=1, keepdim=True) + v for q [b, A, N] and v [b, 1, N], then a softmax over
+    N when asked: one launch each way on the GPU; the torch lines on the CPU, with
+    ``fused`` False, and when A * N exceeds the kernels' LDS row (TSRL_DUELING_MAX_ROW)."""
+    if fused and q.is_cuda and q.dim() == 3 and v.shape == (q.shape[0], 1, q.shape[2]) and \
+            q.dtype == torch.float32 and v.dtype == torch.float32 and q.shape[0] > 0:
+        try:
+            return _DuelingFn.apply(q, v, softmax)
+        except _DuelingRowTooLarge:
+            pass
+    logits = q - q.mean(dim=1, keepdim=True) + v
+    return torch.softmax(logits, dim=-1) if softmax else logits
 
 
 def miniblock(input_size, output_size=0, norm_layer=None, activation=None,
@@ -153,11 +456,19 @@ class MLP(nn.Module):
 
 
 class Net(nn.Module):
-    """common.py:161-285 (no dueling / atoms / concat beyond what PPO uses)."""
+    """common.py:161-285.  ``dueling_param = (q_kwargs, v_kwargs)`` adds the dueling heads
+    ``Q`` and ``V`` (MLPs over the trunk's output, common.py:242-260); their combine, and the
+    softmax after it, are one tsrl_dueling_fwd launch on the GPU (``fused_dueling = False``:
+    the torch lines).  NoisyLinear layers anywhere inside compute one forward with one build of
+    their effective parameters (noisy_hold)."""
+
+    fused_dueling = True
 
     def __init__(self, state_shape, action_shape=0, hidden_sizes: Sequence[int] = (),
                  norm_layer=None, activation=nn.ReLU, device="cpu", softmax: bool = False,
-                 concat: bool = False, num_atoms: int = 1, linear_layer=Linear):
+                 concat: bool = False, num_atoms: int = 1,
+                 dueling_param: Optional[Tuple[Dict[str, Any], Dict[str, Any]]] = None,
+                 linear_layer=Linear):
         super().__init__()
         self.device = device
         self.softmax = softmax
@@ -166,18 +477,48 @@ class Net(nn.Module):
         action_dim = int(np.prod(action_shape)) * num_atoms
         if concat:
             input_dim += action_dim
-        output_dim = action_dim if not concat else 0
+        self.use_dueling = dueling_param is not None
+        output_dim = action_dim if not self.use_dueling and not concat else 0
         self.model = MLP(input_dim, output_dim, hidden_sizes, norm_layer, activation, device,
                          linear_layer)
         self.output_dim = self.model.output_dim
+        if self.use_dueling:
+            q_kwargs, v_kwargs = dueling_param
+            q_output_dim, v_output_dim = 0, 0
+            if not concat:
+                q_output_dim, v_output_dim = action_dim, num_atoms
+            q_kwargs = {**q_kwargs, "input_dim": self.output_dim, "output_dim": q_output_dim,
+                        "device": self.device}
+            v_kwargs = {**v_kwargs, "input_dim": self.output_dim, "output_dim": v_output_dim,
+                        "device": self.device}
+            self.Q, self.V = MLP(**q_kwargs), MLP(**v_kwargs)
+            self.output_dim = self.Q.output_dim
+        else:
+            self.Q, self.V = None, None
+        self._noisy = bool(noisy_layers(self))
 
     def forward(self, obs, state: Any = None, **kwargs):
+        if self._noisy and self.training:
+            with noisy_hold(self):
+                return self._forward(obs), state
+        return self._forward(obs), state
+
+    def _forward(self, obs):
         logits = self.model(obs)
-        if self.num_atoms > 1:
-            logits = logits.view(logits.shape[0], -1, self.num_atoms)
+        batch_size = logits.shape[0]
+        if self.use_dueling:
+            q, v = self.Q(logits), self.V(logits)
+            if self.num_atoms > 1:
+                q = q.view(batch_size, -1, self.num_atoms)
+                v = v.view(batch_size, -1, self.num_atoms)
+                return dueling_combine(q, v, self.softmax, self.fused_dueling)
+            logits = dueling_combine(q.unsqueeze(2), v.unsqueeze(2), False,
+                                     self.fused_dueling).squeeze(2)
+        elif self.num_atoms > 1:
+            logits = logits.view(batch_size, -1, self.num_atoms)
         if self.softmax:
             logits = torch.softmax(logits, dim=-1)
-        return logits, state
+        return logits
 
 
 def _module_device(m: nn.Module):

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from tianshou_amd import _C
-from tianshou_amd.utils.net import sum_rows
+from tianshou_amd.utils.net import Linear, NoisyLinear, dueling_combine, noisy_hold, sum_rows
 
 
 def frames_to_f32_nhwc(obs: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
@@ -481,6 +481,50 @@ class C51(DQN):
         obs, state = super().forward(obs, rows=rows)
         obs = obs.view(-1, self.num_atoms).softmax(dim=-1)
         return obs.view(-1, self.action_num, self.num_atoms), state
+
+
+class Rainbow(DQN):
+    """atari_network.py:121-179: the DQN conv trunk (``features_only``), then the heads ``Q``
+    (Linear 512 - ReLU - Linear A * N) and, with ``is_dueling``, ``V`` (Linear 512 - ReLU -
+    Linear N) of NoisyLinear layers (``is_noisy``) or plain ones; the dueling combine and the
+    softmax over the atoms are one tsrl_dueling_fwd launch on the GPU (``fused_dueling =
+    False``: the torch lines).  Returns probabilities [b, A, N]."""
+
+    fused_dueling = True
+
+    def __init__(self, c: int, h: int, w: int, action_shape: Sequence[int], num_atoms: int = 51,
+                 noisy_std: float = 0.5, device="cpu", is_dueling: bool = True,
+                 is_noisy: bool = True) -> None:
+        super().__init__(c, h, w, action_shape, device, features_only=True)
+        self.action_num = int(np.prod(action_shape))
+        self.num_atoms = num_atoms
+
+        def linear(x, y):
+            return NoisyLinear(x, y, noisy_std) if is_noisy else Linear(x, y)
+
+        self.Q = nn.Sequential(linear(self.output_dim, 512), nn.ReLU(inplace=True),
+                               linear(512, self.action_num * self.num_atoms))
+        self._is_dueling = is_dueling
+        if self._is_dueling:
+            self.V = nn.Sequential(linear(self.output_dim, 512), nn.ReLU(inplace=True),
+                                   linear(512, self.num_atoms))
+        self.output_dim = self.action_num * self.num_atoms
+        self._noisy = bool(is_noisy)
+
+    def forward(self, obs, state: Any = None, info: Dict[str, Any] = {},
+                rows: Optional[torch.Tensor] = None):
+        obs, state = super().forward(obs, rows=rows)
+        if self._noisy and self.training:
+            with noisy_hold(self):
+                return self._heads(obs), state
+        return self._heads(obs), state
+
+    def _heads(self, feat):
+        q = self.Q(feat).view(-1, self.action_num, self.num_atoms)
+        if self._is_dueling:
+            v = self.V(feat).view(-1, 1, self.num_atoms)
+            return dueling_combine(q, v, True, self.fused_dueling)
+        return q.softmax(dim=2)
 
 
 class QRDQN(DQN):

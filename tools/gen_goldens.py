@@ -2808,6 +2808,167 @@ def gen_offpolicy_trainer():
         print(kind, "epochs", epochs, "losses", losses[0])
     _save("offpolicy_trainer.npz", data=np.array(json.dumps(out)))
 
+# --------------------------------------------------------------------------------------
+# 28. RainbowPolicy (tianshou/policy/modelfree/rainbow.py) over a dueling Net of NoisyLinear
+#     heads (utils/net/common.py:242-285, utils/net/discrete.py:319-394): six update() calls
+#     per variant over gen_dqn's add() stream, recorded as gen_dist_dqn records C51.  Every
+#     eps_p / eps_q of both networks is recorded as sample_noise left it, before the update
+#     that uses it (a device generator cannot reproduce the CPU stream); the state_dict after
+#     the update therefore goes without its eps entries.  A committed fixture stays under
+#     1 MiB and one state_dict is 52 KiB, so it is recorded after the updates of
+#     RAINBOW_PARAM_UPDATES only: the last one, and updates that a later sync copies into the
+#     target network; losses, returns, outgoing weights and projected targets, which depend
+#     on every earlier update's parameters, are recorded for all six.  The target network after
+#     a sync is asserted here to be the online parameters of one update earlier with the online
+#     network's fresh noise, so it needs no arrays of its own.
+#     The reference's Net reads self.output_dim ahead of its assignment when dueling_param is
+#     given (common.py:249); _RefDuelingNet supplies the value upstream assigns there, the
+#     trunk's output_dim, and changes nothing else.
+# --------------------------------------------------------------------------------------
+RAINBOW_C51 = dict(num_atoms=51, v_min=-4.0, v_max=4.0)
+RAINBOW_VARIANTS = {
+    "target": dict(freq=2, n_step=1, bs=32, optim="adam"),
+    "per": dict(freq=2, n_step=3, bs=16, optim="adam", per=True),
+    "rms": dict(freq=3, n_step=1, bs=32, optim="rms"),
+    "notarget": dict(freq=0, n_step=1, bs=17, optim="adam"),
+}
+RAINBOW_PARAM_UPDATES = {"target": (0, 1, 3, 5), "per": (1, 5), "rms": (0, 2, 5),
+                         "notarget": (0, 5)}
+RAINBOW_INIT_SEED, RAINBOW_SAMPLE_SEED, RAINBOW_NOISE_SEED, RAINBOW_STD = 11, 8, 5, 0.5
+
+
+def _rainbow_net(Net, NoisyLinear, D, A):
+    def noisy(x, y):
+        return NoisyLinear(x, y, RAINBOW_STD)
+    head = {"hidden_sizes": (16,), "linear_layer": noisy}
+    return Net(D, A, hidden_sizes=(16,), softmax=True, num_atoms=RAINBOW_C51["num_atoms"],
+               dueling_param=(dict(head), dict(head)))
+
+
+def gen_rainbow():
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import RainbowPolicy
+    from tianshou.policy.modelfree import rainbow as ref_rainbow
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.discrete import NoisyLinear, sample_noise
+
+    class _RefDuelingNet(Net):
+        @property
+        def output_dim(self):
+            return self.__dict__.get("_output_dim", self.model.output_dim)
+
+        @output_dim.setter
+        def output_dim(self, value):
+            self.__dict__["_output_dim"] = value
+
+    out = {}
+    E, S, D, A = DQN_E, DQN_S, DQN_D, DQN_A
+    adds = _dqn_adds(np.random.default_rng(41))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    no_eps = lambda sd: {k: t.detach().numpy().copy() for k, t in sd.items()  # noqa: E731
+                         if ".eps_" not in k}
+    for tag, v in RAINBOW_VARIANTS.items():
+        p = tag + "_"
+        if v.get("per"):
+            buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+        else:
+            buf = VectorReplayBuffer(E * S, E)
+        for a in adds:
+            buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                    buffer_ids=a["ids"])
+        torch.manual_seed(RAINBOW_INIT_SEED)
+        net = _rainbow_net(_RefDuelingNet, NoisyLinear, D, A)
+        if v["optim"] == "rms":
+            optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+        else:
+            optim = torch.optim.Adam(net.parameters(), lr=1e-3)
+        policy = RainbowPolicy(net, optim, **RAINBOW_C51, discount_factor=0.97,
+                               estimation_step=v["n_step"], target_update_freq=v["freq"])
+        if not any(k.startswith("init_") for k in out):  # every variant starts here, eps too
+            out.update({"init_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                np.asarray(buf.last_index)
+        process_fn, learn, forward = policy.process_fn, policy.learn, policy.forward
+        seen, gaps, noise = [], [], []
+
+        def rec_sample(model):
+            done = sample_noise(model)
+            which = "model" if model is policy.model else "old"
+            noise[-1].update({f"eps_{which}_{k}": t.numpy().copy()
+                              for k, t in model.state_dict().items() if ".eps_" in k})
+            return done
+
+        def rec_forward(batch, state=None, model="model", input="obs", **kw_):
+            res = forward(batch, state, model=model, input=input, **kw_)
+            if model == "model" and input == "obs_next":
+                z64 = res.logits.detach().double()
+                gaps.append(_top2_gap((z64 * policy.support.double()).sum(2).numpy()))
+            return res
+
+        def rec_process(batch, buffer, indices):
+            batch = process_fn(batch, buffer, indices)
+            seen.append(dict(indices=np.array(indices, copy=True),
+                             returns=batch.returns.detach().numpy().copy()))
+            if hasattr(batch, "weight"):
+                seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+            return batch
+
+        def rec_target_dist(batch):  # the projected target of the update (after its sync)
+            t = target_dist(batch)
+            seen[-1]["target_dist"] = t.detach().numpy().copy()
+            return t
+
+        def rec_learn(batch, **kw_):
+            noise.append({})
+            res = learn(batch, **kw_)
+            seen[-1]["out_weight"] = batch.weight.detach().numpy().copy()
+            return res
+
+        policy.process_fn, policy.learn, policy.forward = rec_process, rec_learn, rec_forward
+        target_dist, policy._target_dist = policy._target_dist, rec_target_dist
+        ref_rainbow.sample_noise = rec_sample
+        np.random.seed(RAINBOW_SAMPLE_SEED)
+        torch.manual_seed(RAINBOW_NOISE_SEED)
+        before = no_eps(net.state_dict())
+        try:
+            for u in range(6):
+                synced = v["freq"] > 0 and policy._iter % v["freq"] == 0
+                res = policy.update(v["bs"], buf)
+                q = p + f"u{u}_"
+                out[q + "loss"] = np.array(res["loss"])
+                for k, a in {**seen[u], **noise[u]}.items():
+                    out[q + k] = a
+                if u in RAINBOW_PARAM_UPDATES[tag]:
+                    out.update({q + "param_" + k: a
+                                for k, a in no_eps(net.state_dict()).items()})
+                if synced:
+                    for k, t in policy.model_old.state_dict().items():
+                        if ".eps_" in k:  # the sync copied the online noise over the target's
+                            assert torch.equal(t, net.state_dict()[k]), (tag, u, k)
+                        else:
+                            assert np.array_equal(t.numpy(), before[k]), (tag, u, k)
+                before = no_eps(net.state_dict())
+                if v.get("per"):
+                    out[q + "leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+        finally:
+            ref_rainbow.sample_noise = sample_noise
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+        assert len(gaps) == 6 and len(noise) == 6, (tag, len(gaps), len(noise))
+        out[p + "top2_gap"] = np.array(min(gaps))
+        print(tag, "top-two gap", min(gaps))
+        assert min(gaps) >= 1e-4, (tag, min(gaps))
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=E, S=S, D=D, A=A, gamma=0.97, hidden=[16], head_hidden=[16], noisy_std=RAINBOW_STD,
+        init_seed=RAINBOW_INIT_SEED, seed=RAINBOW_SAMPLE_SEED, noise_seed=RAINBOW_NOISE_SEED,
+        c51=RAINBOW_C51, variants=RAINBOW_VARIANTS,
+        param_updates={k: list(r) for k, r in RAINBOW_PARAM_UPDATES.items()})))
+    _save("rainbow.npz", **out)
+
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
@@ -2815,7 +2976,7 @@ if __name__ == "__main__":
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
-                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq"]
+                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -2826,6 +2987,6 @@ if __name__ == "__main__":
                  offpolicy_trainer=gen_offpolicy_trainer,
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
-                 redq=gen_redq)
+                 redq=gen_redq, rainbow=gen_rainbow)
     for w in which:
         table[w]()
