@@ -3,14 +3,16 @@ network's parameters views into one flat buffer laid out as the online network's
 parameters, ``target_mirrored`` says whether that still holds.  Neither depends on a device, so
 an f32 buffer with FlatAdam's ``_slot`` views stands in for FlatAdam.flat_param here (bind_adam
 itself needs the HIP library).  The conv case keeps a channels_last weight: a slot that is not
-contiguous."""
+contiguous.  ``KernelGradLoss`` is the backward the off-policy loss functions inherit: a
+stand-in forward that "writes" flat f32 gradients the way their kernels do exercises it."""
 from copy import deepcopy
 
 import pytest
 import torch
 
 from tianshou_amd.policy.flat_adam import _slot
-from tianshou_amd.policy.flat_learn import mirror_target, target_mirrored
+from tianshou_amd.policy.flat_learn import (KernelGradLoss, _unit_seed, mirror_target,
+                                            target_mirrored)
 
 
 def _mlp():
@@ -80,3 +82,29 @@ def test_target_mirror_layout_and_predicate(make):
     again = mirror_target(old, params, flat)
     assert target_mirrored(old, again, flat, flat)
     assert not target_mirrored(old, flat_old, flat, flat)
+
+
+class _StandInLoss(KernelGradLoss):
+    @staticmethod
+    def forward(ctx, args, x, y):
+        grads = [torch.full((t.numel(),), float(k + 2), dtype=torch.float32)
+                 for k, t in enumerate((x, y))]
+        KernelGradLoss.keep(ctx, grads, (x, y))
+        return torch.zeros((), dtype=torch.float32)
+
+
+def test_kernel_grad_loss_backward():
+    def grads_after(seed):
+        x = torch.zeros(3, 2, dtype=torch.float64, requires_grad=True)
+        y = torch.zeros(4, requires_grad=True)
+        _StandInLoss.apply(("not a tensor",), x, y).backward(seed)
+        return x.grad, y.grad
+
+    # scaled by the seed, viewed and cast to each input's shape and dtype
+    gx, gy = grads_after(torch.tensor(0.5))
+    assert gx.dtype == torch.float64 and torch.equal(gx, torch.full((3, 2), 1.0).double())
+    assert gy.dtype == torch.float32 and torch.equal(gy, torch.full((4,), 1.5))
+    # the unit seed hands the kernel's gradients over as they are
+    gx, gy = grads_after(_unit_seed(torch.device("cpu")))
+    assert torch.equal(gx, torch.full((3, 2), 2.0).double())
+    assert torch.equal(gy, torch.full((4,), 3.0))

@@ -8,13 +8,12 @@
 //                        two critics
 //   neg_mean_kernel      the actor loss -Q.mean() (ddpg.py:189) and its constant gradient
 //   act_noise_kernel     exploration_noise (ddpg.py:202) over the caller's NumPy draws
-#include "tsrl_common.h"
+#include "loss_sum.h"
 
 namespace tsrl {
 namespace {
 
-constexpr int TPB = 256;
-constexpr int NW = TPB / kWave;
+constexpr int TPB = kLossTPB;
 constexpr int kMaxSeg = 4;
 constexpr unsigned kMaxBlocks = 1024;
 
@@ -85,31 +84,17 @@ __global__ __launch_bounds__(TPB) void td3_smooth_kernel(const float* a,
     out[i] = a[i] + e;
 }
 
-// One workgroup = 256 rows of every critic.  The loss terms are summed in f64 in a fixed order:
-// lanes by xor butterfly, the four waves in wave order, the workgroups in block order (by this
-// kernel when there is one workgroup, else by q_fold_kernel).
-__device__ __forceinline__ void finish_losses(const double* s, int nk, int64_t b, float sign,
-                                              float* loss, float* total) {
-    double tot = 0.0;
-    for (int k = 0; k < nk; ++k) {
-        const double l = s[k] / (double)b;
-        loss[k] = sign * (float)l;
-        tot += l;
-    }
-    if (total) total[0] = sign * (float)tot;
-}
-
+// One workgroup = 256 rows of the NK critics (q2 and grad2 are read only with NK = 2).  The loss
+// terms are summed in loss_sum.h's fixed order.
+template <int NK>
 __global__ __launch_bounds__(TPB) void q_mse_kernel(
     const float* __restrict__ q1, const float* __restrict__ q2,
     const float* __restrict__ returns, const float* __restrict__ weight, int64_t b, float inv_b,
     float* __restrict__ grad1, float* __restrict__ grad2, float* __restrict__ td_out,
-    double* __restrict__ partials, float* __restrict__ loss, float* __restrict__ total) {
+    double* __restrict__ partials, MeanLosses<NK> fin) {
 #pragma clang fp contract(off)
-    __shared__ double red[2][NW];
-    const int t = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * TPB + t;
-    const int nk = q2 ? 2 : 1;
-    double term[2] = {0.0, 0.0};
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    double term[NK] = {};
     if (r < b) {
         const float ret = returns[r];
         const float w = weight ? weight[r] : 1.0f;
@@ -117,7 +102,7 @@ __global__ __launch_bounds__(TPB) void q_mse_kernel(
         term[0] = (double)(td1 * td1 * w);
         grad1[r] = 2.0f * td1 * w * inv_b;
         float row = td1;
-        if (q2) {
+        if constexpr (NK == 2) {
             const float td2 = q2[r] - ret;
             term[1] = (double)(td2 * td2 * w);
             grad2[r] = 2.0f * td2 * w * inv_b;
@@ -125,58 +110,24 @@ __global__ __launch_bounds__(TPB) void q_mse_kernel(
         }
         td_out[r] = row;
     }
-    for (int k = 0; k < nk; ++k) {
-        const double ws = wave_sum(term[k]);
-        if ((t & (kWave - 1)) == 0) red[k][t / kWave] = ws;
-    }
-    __syncthreads();
-    if (t == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < nk; ++k)
-            for (int i = 0; i < NW; ++i) s[k] += red[k][i];
-        if (gridDim.x == 1) {
-            finish_losses(s, nk, b, 1.0f, loss, total);
-        } else {
-            for (int k = 0; k < nk; ++k) partials[(int64_t)k * gridDim.x + blockIdx.x] = s[k];
-        }
-    }
+    double s[NK];
+    block_sums<NK>(term, s);
+    losses_or_partials<NK>(s, partials, fin);
 }
 
 __global__ __launch_bounds__(TPB) void neg_mean_kernel(const float* __restrict__ q, int64_t b,
                                                        float g, float* __restrict__ grad,
                                                        double* __restrict__ partials,
-                                                       float* __restrict__ loss) {
-    __shared__ double red[NW];
-    const int t = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * TPB + t;
-    double term = 0.0;
+                                                       MeanLosses<1> fin) {
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    double term[1] = {0.0};
     if (r < b) {
-        term = (double)q[r];
+        term[0] = (double)q[r];
         grad[r] = g;
     }
-    const double ws = wave_sum(term);
-    if ((t & (kWave - 1)) == 0) red[t / kWave] = ws;
-    __syncthreads();
-    if (t == 0) {
-        double s = 0.0;
-        for (int i = 0; i < NW; ++i) s += red[i];
-        if (gridDim.x == 1)
-            finish_losses(&s, 1, b, -1.0f, loss, nullptr);
-        else
-            partials[blockIdx.x] = s;
-    }
-}
-
-// partials [nk][nblk] -> loss[k] = sign * sum_blk / b, total (optional) = their sum.
-__global__ void q_fold_kernel(const double* __restrict__ partials, int64_t nblk, int nk,
-                              int64_t b, float sign, float* __restrict__ loss,
-                              float* __restrict__ total) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < nk; ++k)
-            for (int64_t i = 0; i < nblk; ++i) s[k] += partials[(int64_t)k * nblk + i];
-        finish_losses(s, nk, b, sign, loss, total);
-    }
+    double s[1];
+    block_sums<1>(term, s);
+    losses_or_partials<1>(s, partials, fin);
 }
 
 // NumPy's `act + noise` (f32 + f64 -> f64), rounded to the f32 the buffer and the critic use.
@@ -190,6 +141,17 @@ __global__ __launch_bounds__(TPB) void act_noise_kernel(const float* __restrict_
 
 inline unsigned row_blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+template <int NK>
+int launch_q_mse(const float* q1, const float* q2, const float* returns, const float* weight,
+                 int64_t b, float* grad1, float* grad2, float* td_out, double* partials,
+                 float* loss, float* total, hipStream_t st) {
+    const MeanLosses<NK> fin{(double)b, 1.0f, loss, total};
+    return launch_loss<NK>("tsrl_q_mse_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(q_mse_kernel<NK>, dim3(nblk), dim3(TPB), 0, st, q1, q2, returns,
+                           weight, b, 1.0f / (float)b, grad1, grad2, td_out, partials, fin);
+    });
+}
 
 }  // namespace
 }  // namespace tsrl
@@ -237,7 +199,7 @@ extern "C" int tsrl_td3_smooth(const float* act, const float* noise, double sigm
     return 0;
 }
 
-extern "C" int64_t tsrl_ddpg_num_partials(int64_t b) { return b > 0 ? (b + TPB - 1) / TPB : 0; }
+extern "C" int64_t tsrl_ddpg_num_partials(int64_t b) { return loss_blocks(b); }
 
 extern "C" int tsrl_q_mse_fwd_bwd(const float* q1, const float* q2, const float* returns,
                                   const float* weight, int64_t b, float* grad1, float* grad2,
@@ -246,35 +208,21 @@ extern "C" int tsrl_q_mse_fwd_bwd(const float* q1, const float* q2, const float*
     TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) * TPB, "tsrl_q_mse_fwd_bwd: need b >= 1");
     TSRL_CHECK_ARG(q1 && returns && grad1 && td_out && loss && (!q2 || grad2),
                    "tsrl_q_mse_fwd_bwd: null pointer");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_q_mse_fwd_bwd: b > %d needs partials", TPB);
-    hipLaunchKernelGGL(q_mse_kernel, dim3((unsigned)nblk), dim3(TPB), 0, as_stream(stream), q1,
-                       q2, returns, weight, b, 1.0f / (float)b, grad1, grad2, td_out, partials,
-                       loss, total);
-    TSRL_LAUNCH_CHECK("tsrl_q_mse_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(q_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream), partials,
-                           nblk, q2 ? 2 : 1, b, 1.0f, loss, total);
-        TSRL_LAUNCH_CHECK("tsrl_q_mse_fwd_bwd (fold)");
-    }
-    return 0;
+    return (q2 ? launch_q_mse<2> : launch_q_mse<1>)(q1, q2, returns, weight, b, grad1, grad2,
+                                                    td_out, partials, loss, total,
+                                                    as_stream(stream));
 }
 
 extern "C" int tsrl_neg_mean_fwd_bwd(const float* q, int64_t b, float* grad, double* partials,
                                      float* loss, void* stream) {
     TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) * TPB, "tsrl_neg_mean_fwd_bwd: need b >= 1");
     TSRL_CHECK_ARG(q && grad && loss, "tsrl_neg_mean_fwd_bwd: null pointer");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_neg_mean_fwd_bwd: b > %d needs partials", TPB);
-    hipLaunchKernelGGL(neg_mean_kernel, dim3((unsigned)nblk), dim3(TPB), 0, as_stream(stream), q,
-                       b, -1.0f / (float)b, grad, partials, loss);
-    TSRL_LAUNCH_CHECK("tsrl_neg_mean_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(q_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream), partials,
-                           nblk, 1, b, -1.0f, loss, (float*)nullptr);
-        TSRL_LAUNCH_CHECK("tsrl_neg_mean_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const MeanLosses<1> fin{(double)b, -1.0f, loss, nullptr};
+    return launch_loss<1>("tsrl_neg_mean_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(neg_mean_kernel, dim3(nblk), dim3(TPB), 0, st, q, b,
+                           -1.0f / (float)b, grad, partials, fin);
+    });
 }
 
 extern "C" int tsrl_act_noise(const float* act, const double* noise, int64_t n, float* out,

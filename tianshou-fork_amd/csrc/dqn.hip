@@ -3,13 +3,12 @@
 // and exploration_noise's epsilon-greedy overwrite (:190-203).  A DQN minibatch is 32 to a few
 // hundred rows of <= 18 actions, so every kernel is one row per lane with a loop over the
 // actions: the work is launch latency, and each kernel replaces 3-10 torch launches.
-#include "tsrl_common.h"
+#include "loss_sum.h"
 
 namespace tsrl {
 namespace {
 
-constexpr int TPB = 256;
-constexpr int NW = TPB / kWave;
+constexpr int TPB = kLossTPB;
 
 // torch's max / argmax over a row: the first index of the maximum, a NaN beats every number
 // (the first NaN wins).
@@ -38,21 +37,19 @@ __global__ __launch_bounds__(TPB) void target_q_kernel(const float* __restrict__
 
 // One workgroup = 256 rows.  Each lane computes its row's TD error, loss term and the one
 // non-zero gradient entry; the [rows, A] gradient tile is then written by the whole workgroup
-// in storage order (zeros off the taken action).  The loss terms are summed in f64 in a fixed
-// order: lanes by xor butterfly, the four waves in wave order, the workgroups in block order
-// (by this kernel when there is one workgroup, else by td_fold_kernel).
+// in storage order (zeros off the taken action), after block_sums' barrier.  The loss terms are
+// summed in loss_sum.h's fixed order.
 __global__ __launch_bounds__(TPB) void td_fwd_bwd_kernel(
     const float* __restrict__ q, const int64_t* __restrict__ act,
     const float* __restrict__ returns, const float* __restrict__ weight, int64_t b, int64_t A,
     int huber, float inv_b, float* __restrict__ grad_q, float* __restrict__ td_error,
-    double* __restrict__ partials, float* __restrict__ loss) {
+    double* __restrict__ partials, MeanLosses<1> fin) {
     __shared__ float s_g[TPB];
     __shared__ int s_a[TPB];
-    __shared__ double red[NW];
     const int t = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * TPB;
     const int nrows = (int)min((int64_t)TPB, b - r0);
-    double term = 0.0;
+    double term[1] = {0.0};
     float g = 0.0f;
     int a = -1;
     if (t < nrows) {
@@ -64,19 +61,18 @@ __global__ __launch_bounds__(TPB) void td_fwd_bwd_kernel(
         td_error[r] = td;
         if (huber) {  // torch huber_loss, delta 1, on x = q_a - returns = -td
             const float ax = fabsf(td);
-            term = (double)(ax < 1.0f ? 0.5f * td * td : ax - 0.5f);
+            term[0] = (double)(ax < 1.0f ? 0.5f * td * td : ax - 0.5f);
             g = (td >= 1.0f ? -1.0f : td <= -1.0f ? 1.0f : -td) * inv_b;
         } else {
             const float w = weight ? weight[r] : 1.0f;
-            term = (double)(td * td * w);
+            term[0] = (double)(td * td * w);
             g = -2.0f * td * w * inv_b;
         }
     }
     s_g[t] = g;
     s_a[t] = a;
-    const double ws = wave_sum(term);
-    if ((t & (kWave - 1)) == 0) red[t / kWave] = ws;
-    __syncthreads();
+    double s[1];
+    block_sums<1>(term, s);
     const int64_t nel = (int64_t)nrows * A;
     float* g_blk = grad_q + r0 * A;
     for (int64_t f = t; f < nel; f += TPB) {
@@ -84,23 +80,7 @@ __global__ __launch_bounds__(TPB) void td_fwd_bwd_kernel(
         const int col = (int)(f - (int64_t)row * A);
         g_blk[f] = col == s_a[row] ? s_g[row] : 0.0f;
     }
-    if (t == 0) {
-        double s = 0.0;
-        for (int i = 0; i < NW; ++i) s += red[i];
-        if (gridDim.x == 1)
-            loss[0] = (float)(s / (double)b);
-        else
-            partials[blockIdx.x] = s;
-    }
-}
-
-__global__ void td_fold_kernel(const double* __restrict__ partials, int64_t n, int64_t b,
-                               float* __restrict__ loss) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s = 0.0;
-        for (int64_t i = 0; i < n; ++i) s += partials[i];
-        loss[0] = (float)(s / (double)b);
-    }
+    losses_or_partials<1>(s, partials, fin);
 }
 
 // NumPy's f64 arithmetic: q = u_act + mask, the first index of the maximum.
@@ -146,7 +126,7 @@ extern "C" int tsrl_dqn_target_q(const float* q_sel, const float* q_eval, int64_
     return 0;
 }
 
-extern "C" int64_t tsrl_dqn_num_partials(int64_t b) { return b > 0 ? (b + TPB - 1) / TPB : 0; }
+extern "C" int64_t tsrl_dqn_num_partials(int64_t b) { return loss_blocks(b); }
 
 extern "C" int tsrl_dqn_td_fwd_bwd(const float* q, const int64_t* act, const float* returns,
                                    const float* weight, int64_t b, int64_t num_actions,
@@ -156,18 +136,13 @@ extern "C" int tsrl_dqn_td_fwd_bwd(const float* q, const int64_t* act, const flo
                    "tsrl_dqn_td_fwd_bwd: need b >= 1 and num_actions >= 1");
     TSRL_CHECK_ARG(q && act && returns && grad_q && td_error && loss,
                    "tsrl_dqn_td_fwd_bwd: null pointer");
-    const int64_t nblk = tsrl_dqn_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_dqn_td_fwd_bwd: b > %d needs partials", TPB);
-    hipLaunchKernelGGL(td_fwd_bwd_kernel, dim3((unsigned)nblk), dim3(TPB), 0, as_stream(stream),
-                       q, act, returns, weight, b, num_actions, huber, 1.0f / (float)b, grad_q,
-                       td_error, partials, loss);
-    TSRL_LAUNCH_CHECK("tsrl_dqn_td_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(td_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream), partials,
-                           nblk, b, loss);
-        TSRL_LAUNCH_CHECK("tsrl_dqn_td_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const MeanLosses<1> fin{(double)b, 1.0f, loss, nullptr};
+    return launch_loss<1>("tsrl_dqn_td_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(td_fwd_bwd_kernel, dim3(nblk), dim3(TPB), 0, st, q, act, returns,
+                           weight, b, num_actions, huber, 1.0f / (float)b, grad_q, td_error,
+                           partials, fin);
+    });
 }
 
 extern "C" int tsrl_eps_greedy(int64_t* act, const double* u_row, const double* u_act,

@@ -6,7 +6,7 @@
 //   dsac_target_kernel       _target_q after the three forwards (discrete_sac.py:93-97)
 //   dsac_q_loss_kernel       both critics' TD error, loss and [b, A] gradient (:108-124)
 //   dsac_actor_loss_kernel   the actor loss, the temperature loss and every gradient of both
-//                            (:127-144), summed as ddpg.hip sums its losses
+//                            (:127-144), summed in loss_sum.h's order
 // Per row, in f64 on the f32 inputs: m = max_j l_j, S = sum_j exp(l_j - m), lp_j = l_j - m -
 // log S, p_j = exp(lp_j), H = -sum_j p_j lp_j (a term with p_j == 0 is exactly 0), qm_j =
 // min(q1_j, q2_j) (a NaN handed through), V = sum_j p_j qm_j: what Categorical(logits=l)
@@ -17,18 +17,12 @@
 // Groups are aligned inside a wave, so the group reductions are xor butterflies below G; a wave
 // reads 64 / G consecutive rows, i.e. one contiguous span of the row-major table.  The
 // temperature is read from device memory: it changes inside a replayed graph.
-#include "tsrl_common.h"
+#include "loss_sum.h"
 
 namespace tsrl {
 namespace {
 
-constexpr int TPB = 256;  // the loss kernels: one workgroup = tsrl_ddpg_num_partials' 256 rows
-constexpr int NW = TPB / kWave;
-
-// torch.min(a, b): a NaN on either side is handed through.
-__device__ __forceinline__ float min_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b < a ? b : a));
-}
+constexpr int TPB = kLossTPB;
 
 // Butterflies over the G lanes of a group: every lane ends with the same bits (each level adds
 // or compares the same two values on both sides).
@@ -98,32 +92,19 @@ __global__ __launch_bounds__(TPB) void dsac_target_kernel(
     }
 }
 
-// s[k] = sum(td_k^2 * weight): loss[k] = s[k] / b, total (optional) = their sum.
-__device__ __forceinline__ void finish_q_losses(const double* s, int64_t b, float* loss,
-                                                float* total) {
-    double tot = 0.0;
-    for (int k = 0; k < 2; ++k) {
-        const double lk = s[k] / (double)b;
-        loss[k] = (float)lk;
-        tot += lk;
-    }
-    if (total) total[0] = (float)tot;
-}
-
 // One workgroup = 256 rows, one row per lane: its TD errors, loss terms and the one non-zero
 // gradient entry per critic (the taken action's Q is one gathered element per row); the
 // [rows, A] gradient tiles are then written by the whole workgroup in storage order (zeros off
-// the taken action), as dqn.hip's td_fwd_bwd_kernel.  Sums as ddpg.hip's q_mse_kernel.
+// the taken action), as dqn.hip's td_fwd_bwd_kernel.  s[k] = sum(td_k^2 * weight), in
+// loss_sum.h's order.
 __global__ __launch_bounds__(TPB) void dsac_q_loss_kernel(
     const float* __restrict__ q1, const float* __restrict__ q2, const int64_t* __restrict__ act,
     const float* __restrict__ returns, const float* __restrict__ weight, int64_t b, int64_t A,
     float inv_b, float* __restrict__ grad1, float* __restrict__ grad2,
-    float* __restrict__ td_out, double* __restrict__ partials, float* __restrict__ loss,
-    float* __restrict__ total) {
+    float* __restrict__ td_out, double* __restrict__ partials, MeanLosses<2> fin) {
 #pragma clang fp contract(off)
     __shared__ float s_g[2][TPB];
     __shared__ int s_a[TPB];
-    __shared__ double red[2][NW];
     const int t = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * TPB;
     const int nrows = (int)min((int64_t)TPB, b - r0);
@@ -147,11 +128,8 @@ __global__ __launch_bounds__(TPB) void dsac_q_loss_kernel(
     s_g[0][t] = gk[0];
     s_g[1][t] = gk[1];
     s_a[t] = a;
-    for (int k = 0; k < 2; ++k) {
-        const double ws = wave_sum(term[k]);
-        if ((t & (kWave - 1)) == 0) red[k][t / kWave] = ws;
-    }
-    __syncthreads();
+    double s[2];
+    block_sums<2>(term, s);  // its barrier also publishes s_g and s_a
     const int64_t nel = (int64_t)nrows * A;
     float* g1 = grad1 + r0 * A;
     float* g2 = grad2 + r0 * A;
@@ -161,52 +139,18 @@ __global__ __launch_bounds__(TPB) void dsac_q_loss_kernel(
         g1[f] = hit ? s_g[0][row] : 0.0f;
         g2[f] = hit ? s_g[1][row] : 0.0f;
     }
-    if (t == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int i = 0; i < NW; ++i) s[k] += red[k][i];
-        if (gridDim.x == 1) {
-            finish_q_losses(s, b, loss, total);
-        } else {
-            for (int k = 0; k < 2; ++k) partials[(int64_t)k * gridDim.x + blockIdx.x] = s[k];
-        }
-    }
-}
-
-// partials [2][nblk] -> the two losses and their sum.
-__global__ void dsac_q_fold_kernel(const double* __restrict__ partials, int64_t nblk, int64_t b,
-                                   float* __restrict__ loss, float* __restrict__ total) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int64_t i = 0; i < nblk; ++i) s[k] += partials[(int64_t)k * nblk + i];
-        finish_q_losses(s, b, loss, total);
-    }
-}
-
-// s[0] = sum(alpha H + V), s[1] = sum(target_entropy - H).
-__device__ __forceinline__ void finish_dsac_losses(const double* s, int64_t b,
-                                                   const float* log_alpha, float* loss,
-                                                   float* g_log_alpha) {
-    loss[0] = (float)(-(s[0] / (double)b));
-    if (log_alpha) {
-        const double m = s[1] / (double)b;
-        loss[1] = (float)(-(double)log_alpha[0] * m);
-        g_log_alpha[0] = (float)(-m);
-    }
+    losses_or_partials<2>(s, partials, fin);
 }
 
 // One workgroup = 256 rows in G passes of TPB / G rows each; the first lane of a group carries
-// its rows' loss terms.  The sums are f64 in the fixed order of ddpg.hip's q_mse_kernel: a
-// lane's passes in pass order, lanes by xor butterfly, the four waves in wave order, the
-// workgroups in block order (by this kernel when there is one, else by dsac_fold_kernel).
+// its rows' loss terms: s[0] = sum(alpha H + V), s[1] = sum(target_entropy - H), a lane's
+// passes in pass order and then loss_sum.h's order.
 __global__ __launch_bounds__(TPB) void dsac_actor_loss_kernel(
     const float* __restrict__ logits, const float* __restrict__ q1, const float* __restrict__ q2,
-    const float* __restrict__ alpha, const float* __restrict__ log_alpha, double target_entropy,
-    int64_t b, int64_t A, int G, double inv_b, float* __restrict__ g_logits,
-    double* __restrict__ partials, float* __restrict__ loss, float* __restrict__ g_log_alpha) {
+    const float* __restrict__ alpha, double target_entropy, int64_t b, int64_t A, int G,
+    double inv_b, float* __restrict__ g_logits, double* __restrict__ partials,
+    ActorAlphaLosses fin) {
 #pragma clang fp contract(off)
-    __shared__ double red[2][NW];
     const int t = threadIdx.x;
     const int g = t & (G - 1);
     const int rpp = TPB / G;  // rows per pass
@@ -235,33 +179,9 @@ __global__ __launch_bounds__(TPB) void dsac_actor_loss_kernel(
             }
         }
     }
-    for (int k = 0; k < 2; ++k) {
-        const double ws = wave_sum(term[k]);
-        if ((t & (kWave - 1)) == 0) red[k][t / kWave] = ws;
-    }
-    __syncthreads();
-    if (t == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int i = 0; i < NW; ++i) s[k] += red[k][i];
-        if (gridDim.x == 1) {
-            finish_dsac_losses(s, b, log_alpha, loss, g_log_alpha);
-        } else {
-            for (int k = 0; k < 2; ++k) partials[(int64_t)k * gridDim.x + blockIdx.x] = s[k];
-        }
-    }
-}
-
-// partials [2][nblk] -> the losses and the temperature gradient.
-__global__ void dsac_fold_kernel(const double* __restrict__ partials, int64_t nblk, int64_t b,
-                                 const float* __restrict__ log_alpha, float* __restrict__ loss,
-                                 float* __restrict__ g_log_alpha) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int64_t i = 0; i < nblk; ++i) s[k] += partials[(int64_t)k * nblk + i];
-        finish_dsac_losses(s, b, log_alpha, loss, g_log_alpha);
-    }
+    double s[2];
+    block_sums<2>(term, s);
+    losses_or_partials<2>(s, partials, fin);
 }
 
 // The power of two >= A, at most one wave.
@@ -304,18 +224,12 @@ extern "C" int tsrl_dsac_q_loss_fwd_bwd(const float* q1, const float* q2, const 
     if (b == 0) return 0;
     TSRL_CHECK_ARG(q1 && q2 && act && returns && grad1 && grad2 && td_out && loss,
                    "tsrl_dsac_q_loss_fwd_bwd: null pointer");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_dsac_q_loss_fwd_bwd: b > %d needs partials", TPB);
-    hipLaunchKernelGGL(dsac_q_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0, as_stream(stream),
-                       q1, q2, act, returns, weight, b, A, 1.0f / (float)b, grad1, grad2, td_out,
-                       partials, loss, total);
-    TSRL_LAUNCH_CHECK("tsrl_dsac_q_loss_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(dsac_q_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
-                           partials, nblk, b, loss, total);
-        TSRL_LAUNCH_CHECK("tsrl_dsac_q_loss_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const MeanLosses<2> fin{(double)b, 1.0f, loss, total};
+    return launch_loss<2>("tsrl_dsac_q_loss_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(dsac_q_loss_kernel, dim3(nblk), dim3(TPB), 0, st, q1, q2, act, returns,
+                           weight, b, A, 1.0f / (float)b, grad1, grad2, td_out, partials, fin);
+    });
 }
 
 extern "C" int tsrl_dsac_actor_loss_fwd_bwd(const float* logits, const float* q1,
@@ -331,18 +245,11 @@ extern "C" int tsrl_dsac_actor_loss_fwd_bwd(const float* logits, const float* q1
                    "tsrl_dsac_actor_loss_fwd_bwd: null pointer");
     TSRL_CHECK_ARG(!log_alpha || g_log_alpha,
                    "tsrl_dsac_actor_loss_fwd_bwd: log_alpha needs g_log_alpha");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_dsac_actor_loss_fwd_bwd: b > %d needs partials",
-                   TPB);
-    hipLaunchKernelGGL(dsac_actor_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0,
-                       as_stream(stream), logits, q1, q2, alpha, log_alpha,
-                       target_entropy, b, A, group_lanes(A), 1.0 / (double)b, g_logits,
-                       partials, loss, g_log_alpha);
-    TSRL_LAUNCH_CHECK("tsrl_dsac_actor_loss_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(dsac_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream), partials,
-                           nblk, b, log_alpha, loss, g_log_alpha);
-        TSRL_LAUNCH_CHECK("tsrl_dsac_actor_loss_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const ActorAlphaLosses fin{(double)b, -1.0, log_alpha, loss, g_log_alpha};
+    return launch_loss<2>("tsrl_dsac_actor_loss_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(dsac_actor_loss_kernel, dim3(nblk), dim3(TPB), 0, st, logits, q1, q2,
+                           alpha, target_entropy, b, A, group_lanes(A), 1.0 / (double)b, g_logits,
+                           partials, fin);
+    });
 }

@@ -10,40 +10,16 @@
 //                            gradient of both (redq.py:176-189)
 // q is [E, b] row-major, the critics' [E, b, 1] output: one lane owns column i and walks the E
 // members, so every load is coalesced along i and a column's quantities need no cross-lane
-// work.  The batch sums are f64 in the fixed order of ddpg.hip's q_mse_kernel.  The temperature
-// is read from device memory: it changes inside a replayed graph.
+// work.  The batch sums are f64 in loss_sum.h's fixed order.  The temperature is read from
+// device memory: it changes inside a replayed graph.
 #include <cmath>
 
-#include "tsrl_common.h"
+#include "loss_sum.h"
 
 namespace tsrl {
 namespace {
 
-constexpr int TPB = 256;   // one workgroup = tsrl_ddpg_num_partials' 256 columns
-constexpr int NW = TPB / kWave;
-
-// torch.min: a NaN on either side is handed through.
-__device__ __forceinline__ float min_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b < a ? b : a));
-}
-
-// The block's f64 sums: lanes by xor butterfly, the four waves in wave order.  Lane 0 returns
-// the sums in s[0..nk).
-template <int NK>
-__device__ __forceinline__ void block_sums(const double* term, double (*red)[NW], double* s) {
-    const int t = threadIdx.x;
-    for (int k = 0; k < NK; ++k) {
-        const double ws = wave_sum(term[k]);
-        if ((t & (kWave - 1)) == 0) red[k][t / kWave] = ws;
-    }
-    __syncthreads();
-    if (t == 0) {
-        for (int k = 0; k < NK; ++k) {
-            s[k] = 0.0;
-            for (int i = 0; i < NW; ++i) s[k] += red[k][i];
-        }
-    }
-}
+constexpr int TPB = kLossTPB;  // one workgroup = 256 columns
 
 // mode 0: min over the subset; mode 1: its mean, summed in f64 in subset order.  The product and
 // the difference are two f32 roundings (no FMA), as torch's `target_q -= alpha * log_prob`.  The
@@ -68,16 +44,12 @@ __global__ __launch_bounds__(TPB) void redq_target_kernel(
     out[i] = r - p;
 }
 
-__device__ __forceinline__ void finish_q_loss(double s, int64_t E, int64_t b, float* loss) {
-    loss[0] = (float)(s / ((double)E * (double)b));
-}
-
+// s[0] = sum_i sum_e(td[e, i]^2 * weight[i]), a column's E terms first, in index order.
 __global__ __launch_bounds__(TPB) void redq_q_loss_kernel(
     const float* __restrict__ q, const float* __restrict__ returns,
     const float* __restrict__ weight, int64_t E, int64_t b, float inv_n, float* __restrict__ gq,
-    float* __restrict__ td_mean, double* __restrict__ partials, float* __restrict__ loss) {
+    float* __restrict__ td_mean, double* __restrict__ partials, MeanLosses<1> fin) {
 #pragma clang fp contract(off)
-    __shared__ double red[1][NW];
     const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
     double term[1] = {0.0};
     if (i < b) {
@@ -93,44 +65,17 @@ __global__ __launch_bounds__(TPB) void redq_q_loss_kernel(
         td_mean[i] = (float)(tds / (double)E);
     }
     double s[1];
-    block_sums<1>(term, red, s);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1)
-            finish_q_loss(s[0], E, b, loss);
-        else
-            partials[blockIdx.x] = s[0];
-    }
-}
-
-__global__ void redq_q_fold_kernel(const double* __restrict__ partials, int64_t nblk, int64_t E,
-                                   int64_t b, float* __restrict__ loss) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s = 0.0;
-        for (int64_t i = 0; i < nblk; ++i) s += partials[i];
-        finish_q_loss(s, E, b, loss);
-    }
+    block_sums<1>(term, s);
+    losses_or_partials<1>(s, partials, fin);
 }
 
 // s[0] = sum_i(alpha * log_prob[i] - mean_e q[e, i]), s[1] = sum_i(log_prob[i] + target_entropy).
-__device__ __forceinline__ void finish_actor_losses(const double* s, int64_t b,
-                                                    const float* log_alpha, float* loss,
-                                                    float* g_log_alpha) {
-    loss[0] = (float)(s[0] / (double)b);
-    if (log_alpha) {
-        const double m = s[1] / (double)b;
-        loss[1] = (float)(-(double)log_alpha[0] * m);
-        g_log_alpha[0] = (float)(-m);
-    }
-}
-
 __global__ __launch_bounds__(TPB) void redq_actor_loss_kernel(
     const float* __restrict__ q, const float* __restrict__ log_prob,
-    const float* __restrict__ alpha, const float* __restrict__ log_alpha, float target_entropy,
-    int64_t E, int64_t b, float g_q, float inv_b, float* __restrict__ gq,
-    float* __restrict__ g_logp, double* __restrict__ partials, float* __restrict__ loss,
-    float* __restrict__ g_log_alpha) {
+    const float* __restrict__ alpha, float target_entropy, int64_t E, int64_t b, float g_q,
+    float inv_b, float* __restrict__ gq, float* __restrict__ g_logp,
+    double* __restrict__ partials, ActorAlphaLosses fin) {
 #pragma clang fp contract(off)
-    __shared__ double red[2][NW];
     const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
     const float al = alpha[0];
     double term[2] = {0.0, 0.0};
@@ -147,26 +92,8 @@ __global__ __launch_bounds__(TPB) void redq_actor_loss_kernel(
         g_logp[i] = al * inv_b;
     }
     double s[2];
-    block_sums<2>(term, red, s);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1) {
-            finish_actor_losses(s, b, log_alpha, loss, g_log_alpha);
-        } else {
-            for (int k = 0; k < 2; ++k) partials[(int64_t)k * gridDim.x + blockIdx.x] = s[k];
-        }
-    }
-}
-
-// partials [2][nblk] -> the losses and the temperature gradient.
-__global__ void redq_actor_fold_kernel(const double* __restrict__ partials, int64_t nblk,
-                                       int64_t b, const float* __restrict__ log_alpha,
-                                       float* __restrict__ loss, float* __restrict__ g_log_alpha) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int64_t i = 0; i < nblk; ++i) s[k] += partials[(int64_t)k * nblk + i];
-        finish_actor_losses(s, b, log_alpha, loss, g_log_alpha);
-    }
+    block_sums<2>(term, s);
+    losses_or_partials<2>(s, partials, fin);
 }
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
@@ -207,21 +134,14 @@ extern "C" int tsrl_redq_q_loss_fwd_bwd(const float* q, const float* returns,
     TSRL_CHECK_ARG(shape_ok(E, b), "tsrl_redq_q_loss_fwd_bwd: need E >= 1 and b >= 1");
     TSRL_CHECK_ARG(q && returns && gq && td_mean && loss,
                    "tsrl_redq_q_loss_fwd_bwd: null pointer");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_redq_q_loss_fwd_bwd: b > %d needs partials",
-                   TPB);
     // 1 / (E b) rounded once; with E = 1 it is tsrl_q_mse_fwd_bwd's 1 / b
     const float inv_n = (float)(1.0 / ((double)E * (double)b));
-    hipLaunchKernelGGL(redq_q_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0,
-                       as_stream(stream), q, returns, weight, E, b, inv_n, gq, td_mean, partials,
-                       loss);
-    TSRL_LAUNCH_CHECK("tsrl_redq_q_loss_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(redq_q_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
-                           partials, nblk, E, b, loss);
-        TSRL_LAUNCH_CHECK("tsrl_redq_q_loss_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const MeanLosses<1> fin{(double)E * (double)b, 1.0f, loss, nullptr};
+    return launch_loss<1>("tsrl_redq_q_loss_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(redq_q_loss_kernel, dim3(nblk), dim3(TPB), 0, st, q, returns, weight,
+                           E, b, inv_n, gq, td_mean, partials, fin);
+    });
 }
 
 extern "C" int tsrl_redq_actor_loss_fwd_bwd(const float* q, const float* log_prob,
@@ -234,18 +154,12 @@ extern "C" int tsrl_redq_actor_loss_fwd_bwd(const float* q, const float* log_pro
                    "tsrl_redq_actor_loss_fwd_bwd: null pointer");
     TSRL_CHECK_ARG(!log_alpha || g_log_alpha,
                    "tsrl_redq_actor_loss_fwd_bwd: log_alpha needs g_log_alpha");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_redq_actor_loss_fwd_bwd: b > %d needs partials",
-                   TPB);
     const float g_q = (float)(-1.0 / ((double)E * (double)b));
-    hipLaunchKernelGGL(redq_actor_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0,
-                       as_stream(stream), q, log_prob, alpha, log_alpha, (float)target_entropy,
-                       E, b, g_q, 1.0f / (float)b, gq, g_logp, partials, loss, g_log_alpha);
-    TSRL_LAUNCH_CHECK("tsrl_redq_actor_loss_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(redq_actor_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
-                           partials, nblk, b, log_alpha, loss, g_log_alpha);
-        TSRL_LAUNCH_CHECK("tsrl_redq_actor_loss_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const ActorAlphaLosses fin{(double)b, 1.0, log_alpha, loss, g_log_alpha};
+    return launch_loss<2>("tsrl_redq_actor_loss_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(redq_actor_loss_kernel, dim3(nblk), dim3(TPB), 0, st, q, log_prob,
+                           alpha, (float)target_entropy, E, b, g_q, 1.0f / (float)b, gq, g_logp,
+                           partials, fin);
+    });
 }

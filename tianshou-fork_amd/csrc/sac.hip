@@ -7,23 +7,17 @@
 //   sac_sample_bwd_kernel   its analytic gradient towards mu and sigma
 //   sac_target_kernel       _target_q's min(Q1, Q2) - alpha * log_prob (sac.py:141-144)
 //   sac_actor_loss_kernel   the actor loss, the temperature loss and every gradient of both
-//                           (sac.py:162-165, 171-173), summed as ddpg.hip sums its losses
+//                           (sac.py:162-165, 171-173), summed in loss_sum.h's order
 // The temperature is read from device memory in every kernel: it changes inside a replayed graph.
-#include "tsrl_common.h"
+#include "loss_sum.h"
 
 namespace tsrl {
 namespace {
 
-constexpr int TPB = 256;   // the loss kernel: one workgroup = tsrl_ddpg_num_partials' 256 rows
-constexpr int NW = TPB / kWave;
+constexpr int TPB = kLossTPB;
 constexpr int RPB = 64;    // the sample forward: one row per lane, one wave per workgroup
 constexpr float kEps32 = 0x1p-23f;                  // np.finfo(np.float32).eps
 constexpr float kLogSqrt2Pi = 0.91893853320467274f;  // math.log(math.sqrt(2 * math.pi))
-
-// torch.min(a, b): a NaN on either side is handed through.
-__device__ __forceinline__ float min_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b < a ? b : a));
-}
 
 // One lane = one row: its A terms are summed in f64 in index order.  Every term is the f32
 // expression torch evaluates (Normal.log_prob, then log((1 - act^2) + eps32)), no FMA.
@@ -88,31 +82,15 @@ __global__ __launch_bounds__(TPB) void sac_target_kernel(
     out[r] = min_nan(q1[r], q2[r]) - p;
 }
 
-// s[0] = sum(alpha * log_prob - min(q1, q2)), s[1] = sum(log_prob + target_entropy).
-__device__ __forceinline__ void finish_sac_losses(const double* s, int64_t b,
-                                                  const float* log_alpha, float* loss,
-                                                  float* g_log_alpha) {
-    loss[0] = (float)(s[0] / (double)b);
-    if (log_alpha) {
-        const double m = s[1] / (double)b;
-        loss[1] = (float)(-(double)log_alpha[0] * m);
-        g_log_alpha[0] = (float)(-m);
-    }
-}
-
-// One workgroup = 256 rows.  The sums are f64 in the fixed order of ddpg.hip's q_mse_kernel:
-// lanes by xor butterfly, the four waves in wave order, the workgroups in block order (by this
-// kernel when there is one workgroup, else by sac_fold_kernel).
+// One workgroup = 256 rows: s[0] = sum(alpha * log_prob - min(q1, q2)), s[1] = sum(log_prob +
+// target_entropy), in loss_sum.h's fixed order.
 __global__ __launch_bounds__(TPB) void sac_actor_loss_kernel(
     const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ log_prob,
-    const float* __restrict__ alpha, const float* __restrict__ log_alpha, float target_entropy,
-    int64_t b, float inv_b, float* __restrict__ g_q1, float* __restrict__ g_q2,
-    float* __restrict__ g_logp, double* __restrict__ partials, float* __restrict__ loss,
-    float* __restrict__ g_log_alpha) {
+    const float* __restrict__ alpha, float target_entropy, int64_t b, float inv_b,
+    float* __restrict__ g_q1, float* __restrict__ g_q2, float* __restrict__ g_logp,
+    double* __restrict__ partials, ActorAlphaLosses fin) {
 #pragma clang fp contract(off)
-    __shared__ double red[2][NW];
-    const int t = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * TPB + t;
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
     const float al = alpha[0];
     double term[2] = {0.0, 0.0};
     if (r < b) {
@@ -128,33 +106,9 @@ __global__ __launch_bounds__(TPB) void sac_actor_loss_kernel(
         g_q2[r] = a < c ? 0.0f : gt;
         g_logp[r] = al * inv_b;
     }
-    for (int k = 0; k < 2; ++k) {
-        const double ws = wave_sum(term[k]);
-        if ((t & (kWave - 1)) == 0) red[k][t / kWave] = ws;
-    }
-    __syncthreads();
-    if (t == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int i = 0; i < NW; ++i) s[k] += red[k][i];
-        if (gridDim.x == 1) {
-            finish_sac_losses(s, b, log_alpha, loss, g_log_alpha);
-        } else {
-            for (int k = 0; k < 2; ++k) partials[(int64_t)k * gridDim.x + blockIdx.x] = s[k];
-        }
-    }
-}
-
-// partials [2][nblk] -> the losses and the temperature gradient.
-__global__ void sac_fold_kernel(const double* __restrict__ partials, int64_t nblk, int64_t b,
-                                const float* __restrict__ log_alpha, float* __restrict__ loss,
-                                float* __restrict__ g_log_alpha) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s[2] = {0.0, 0.0};
-        for (int k = 0; k < 2; ++k)
-            for (int64_t i = 0; i < nblk; ++i) s[k] += partials[(int64_t)k * nblk + i];
-        finish_sac_losses(s, b, log_alpha, loss, g_log_alpha);
-    }
+    double s[2];
+    block_sums<2>(term, s);
+    losses_or_partials<2>(s, partials, fin);
 }
 
 inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -213,18 +167,11 @@ extern "C" int tsrl_sac_actor_loss_fwd_bwd(const float* q1, const float* q2,
                    "tsrl_sac_actor_loss_fwd_bwd: null pointer");
     TSRL_CHECK_ARG(!log_alpha || g_log_alpha,
                    "tsrl_sac_actor_loss_fwd_bwd: log_alpha needs g_log_alpha");
-    const int64_t nblk = tsrl_ddpg_num_partials(b);
-    TSRL_CHECK_ARG(nblk == 1 || partials, "tsrl_sac_actor_loss_fwd_bwd: b > %d needs partials",
-                   TPB);
-    hipLaunchKernelGGL(sac_actor_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0,
-                       as_stream(stream), q1, q2, log_prob, alpha, log_alpha,
-                       (float)target_entropy, b, 1.0f / (float)b, g_q1, g_q2, g_logp, partials,
-                       loss, g_log_alpha);
-    TSRL_LAUNCH_CHECK("tsrl_sac_actor_loss_fwd_bwd");
-    if (nblk > 1) {
-        hipLaunchKernelGGL(sac_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream), partials,
-                           nblk, b, log_alpha, loss, g_log_alpha);
-        TSRL_LAUNCH_CHECK("tsrl_sac_actor_loss_fwd_bwd (fold)");
-    }
-    return 0;
+    const hipStream_t st = as_stream(stream);
+    const ActorAlphaLosses fin{(double)b, 1.0, log_alpha, loss, g_log_alpha};
+    return launch_loss<2>("tsrl_sac_actor_loss_fwd_bwd", b, partials, fin, st, [&](unsigned nblk) {
+        hipLaunchKernelGGL(sac_actor_loss_kernel, dim3(nblk), dim3(TPB), 0, st, q1, q2, log_prob,
+                           alpha, (float)target_entropy, b, 1.0f / (float)b, g_q1, g_q2, g_logp,
+                           partials, fin);
+    });
 }

@@ -36,9 +36,9 @@ from tianshou_amd.data.batch import Batch
 from tianshou_amd.exploration import BaseNoise, GaussianNoise
 from tianshou_amd.policy.base import BasePolicy
 from tianshou_amd.policy.flat_adam import FlatAdam
-from tianshou_amd.policy.flat_learn import (f32_rows, flat_backward, mirror_target,
-                                            replay_learn_graph, target_mirrored)
-from tianshou_amd.policy.onpolicy import _is_unit_seed, _unit_seed
+from tianshou_amd.policy.flat_learn import (KernelGradLoss, _partials, _unit_seed, f32_rows,
+                                            flat_backward, mirror_target, replay_learn_graph,
+                                            target_mirrored)
 from tianshou_amd.utils.capture import graph_capture
 
 SOFT_UPDATE_MAX_SEGMENTS = 4
@@ -72,12 +72,7 @@ def act_noise_device(act: torch.Tensor, noise: np.ndarray) -> torch.Tensor:
     return out
 
 
-def _partials(b: int, per_row: int, dev) -> Optional[torch.Tensor]:
-    nparts = int(_C.lib().tsrl_ddpg_num_partials(b))
-    return torch.empty(per_row * nparts, dtype=torch.float64, device=dev) if nparts > 1 else None
-
-
-class _QMSELoss(torch.autograd.Function):
+class _QMSELoss(KernelGradLoss):
     """ddpg.py:173-178 for one or two critics as tsrl_q_mse_fwd_bwd.  The output is the sum of
     the critics' losses, the handle to call backward on; the per-critic losses and the per-row
     vector are written to ``loss`` / ``td`` (see q_mse_loss)."""
@@ -100,16 +95,8 @@ class _QMSELoss(torch.autograd.Function):
             _C.ptr(grads[1]) if len(x) > 1 else None, _C.ptr(td, torch.float32),
             _C.ptr(_partials(b, 2, dev)), _C.ptr(loss, torch.float32), _C.ptr(total),
             _C.stream_ptr(dev)), "tsrl_q_mse_fwd_bwd")
-        ctx.save_for_backward(*grads)
-        ctx.q_meta = [(q.shape, q.dtype) for q in qs]
+        KernelGradLoss.keep(ctx, grads, qs)
         return total
-
-    @staticmethod
-    def backward(ctx, g):
-        grads = ctx.saved_tensors
-        if not _is_unit_seed(g):  # backward(UNIT): the kernel's gradients as they are
-            grads = [t * g for t in grads]
-        return (None, *(t.view(shape).to(dtype) for t, (shape, dtype) in zip(grads, ctx.q_meta)))
 
 
 def q_mse_loss(qs: Sequence[torch.Tensor], returns: torch.Tensor,
@@ -125,7 +112,7 @@ def q_mse_loss(qs: Sequence[torch.Tensor], returns: torch.Tensor,
     return _QMSELoss.apply((returns, weight, td, loss), *qs), loss, td
 
 
-class _NegMeanLoss(torch.autograd.Function):
+class _NegMeanLoss(KernelGradLoss):
     """ddpg.py:189's -Q.mean() as tsrl_neg_mean_fwd_bwd; with ``loss_out`` the loss goes there
     and the output is only the handle to call backward on."""
 
@@ -141,16 +128,8 @@ class _NegMeanLoss(torch.autograd.Function):
         _C.check(_C.lib().tsrl_neg_mean_fwd_bwd(
             _C.ptr(x), b, _C.ptr(grad), _C.ptr(_partials(b, 1, dev)),
             _C.ptr(loss, torch.float32), _C.stream_ptr(dev)), "tsrl_neg_mean_fwd_bwd")
-        ctx.save_for_backward(grad)
-        ctx.q_meta = (q.shape, q.dtype)
+        KernelGradLoss.keep(ctx, (grad,), (q,))
         return handle
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        if not _is_unit_seed(g):
-            grad = grad * g
-        return None, grad.view(ctx.q_meta[0]).to(ctx.q_meta[1])
 
 
 def neg_mean_loss(q: torch.Tensor, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:

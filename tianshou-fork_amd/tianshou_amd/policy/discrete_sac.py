@@ -32,8 +32,7 @@ from torch.distributions import Categorical
 
 from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
-from tianshou_amd.policy.ddpg import _partials
-from tianshou_amd.policy.onpolicy import _is_unit_seed
+from tianshou_amd.policy.flat_learn import KernelGradLoss, _partials
 from tianshou_amd.policy.pg import gumbel_sample
 from tianshou_amd.policy.sac import SACPolicy
 
@@ -60,7 +59,7 @@ def dsac_target_device(logits: torch.Tensor, q1: torch.Tensor, q2: torch.Tensor,
     return out
 
 
-class _DsacQLoss(torch.autograd.Function):
+class _DsacQLoss(KernelGradLoss):
     """discrete_sac.py:108-124 for both critics as tsrl_dsac_q_loss_fwd_bwd.  The output is the
     sum of the two losses, the handle to call backward on; the per-critic losses and the
     per-row vector are written to ``loss`` / ``td`` (see dsac_q_loss)."""
@@ -83,16 +82,8 @@ class _DsacQLoss(torch.autograd.Function):
             _C.ptr(td, torch.float32), _C.ptr(_partials(b, 2, dev)),
             _C.ptr(loss, torch.float32), _C.ptr(total), _C.stream_ptr(dev)),
             "tsrl_dsac_q_loss_fwd_bwd")
-        ctx.save_for_backward(*grads)
-        ctx.q_meta = [q.dtype for q in (q1, q2)]
+        KernelGradLoss.keep(ctx, grads, (q1, q2))
         return total
-
-    @staticmethod
-    def backward(ctx, g):
-        grads = ctx.saved_tensors
-        if not _is_unit_seed(g):  # backward(UNIT): the kernel's gradients as they are
-            grads = [t * g for t in grads]
-        return (None, *(t.to(dtype) for t, dtype in zip(grads, ctx.q_meta)))
 
 
 def dsac_q_loss(q1: torch.Tensor, q2: torch.Tensor, act: torch.Tensor, returns: torch.Tensor,
@@ -108,7 +99,7 @@ def dsac_q_loss(q1: torch.Tensor, q2: torch.Tensor, act: torch.Tensor, returns: 
     return _DsacQLoss.apply((act, returns, weight, td, loss), q1, q2), loss, td
 
 
-class _DsacActorLoss(torch.autograd.Function):
+class _DsacActorLoss(KernelGradLoss):
     """discrete_sac.py:127-133 and 138-140 as tsrl_dsac_actor_loss_fwd_bwd.  The output is the
     handle to call backward on (towards the logits alone: the critics' tables are constants);
     the losses go to ``loss`` and the temperature's gradient to ``g_log_alpha``."""
@@ -130,16 +121,8 @@ class _DsacActorLoss(torch.autograd.Function):
             _C.ptr(_partials(b, 2, dev)), _C.ptr(loss, torch.float32),
             _C.ptr(g_log_alpha, torch.float32), _C.stream_ptr(dev)),
             "tsrl_dsac_actor_loss_fwd_bwd")
-        ctx.save_for_backward(grad)
-        ctx.meta = logits.dtype
+        KernelGradLoss.keep(ctx, (grad,), (logits,))
         return torch.empty((), dtype=torch.float32, device=dev)
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        if not _is_unit_seed(g):
-            grad = grad * g
-        return None, grad.to(ctx.meta)
 
 
 def dsac_actor_loss(logits: torch.Tensor, q1: torch.Tensor, q2: torch.Tensor,

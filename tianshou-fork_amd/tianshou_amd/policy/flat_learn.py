@@ -2,13 +2,15 @@
 target network mirrored into a flat buffer (DQNPolicy._flat_adam, DDPGPolicy._bind), the
 bracket around a backward into flat gradient buckets (DQNPolicy._step,
 DDPGPolicy._backward_step, FusedLearnMixin._cat_minibatch) and the per-key cache of captured
-off-policy updates (DQNPolicy._graph_step, DDPGPolicy._graph_step)."""
+off-policy updates (DQNPolicy._graph_step, DDPGPolicy._graph_step), and the backward of the
+off-policy losses whose kernel has already written the gradients (KernelGradLoss)."""
 import contextlib
 import warnings
 from typing import Callable, Dict, Iterable, Optional, Sequence
 
 import torch
 
+from tianshou_amd import _C
 from tianshou_amd.policy.flat_adam import FlatAdam, _slot
 
 
@@ -60,6 +62,49 @@ def flat_backward(fas: Iterable[FlatAdam], eager: bool = True):
     if gather:
         for fa in fas:
             fa.gather_grads()
+
+
+_UNIT = {}
+
+
+def _unit_seed(dev: torch.device) -> torch.Tensor:
+    """A constant f32 1.0 on dev, the seed gradient of the Categorical minibatch's
+    loss.backward(): it spares autograd's ones_like fill, and _CatPPOLoss recognises it and
+    skips two scaling passes (round 6).  Never written."""
+    t = _UNIT.get(dev)
+    if t is None:
+        t = _UNIT[dev] = torch.ones((), dtype=torch.float32, device=dev)
+    return t
+
+
+def _is_unit_seed(g: torch.Tensor) -> bool:
+    t = _UNIT.get(g.device)
+    return t is not None and g.dim() == 0 and g.data_ptr() == t.data_ptr()
+
+
+class KernelGradLoss(torch.autograd.Function):
+    """Base of the off-policy losses whose forward kernel writes the gradients as well:
+    ``forward(ctx, args, *inputs)`` ends with ``KernelGradLoss.keep(ctx, grads, inputs)`` and
+    returns the scalar handle to call backward on."""
+
+    @staticmethod
+    def keep(ctx, grads: Sequence[torch.Tensor], inputs: Sequence[torch.Tensor]) -> None:
+        ctx.save_for_backward(*grads)
+        ctx.meta = [(t.shape, t.dtype) for t in inputs]
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = ctx.saved_tensors
+        if not _is_unit_seed(g):  # backward(UNIT): the kernel's gradients as they are
+            grads = [t * g for t in grads]
+        return (None, *(t.view(shape).to(dtype) for t, (shape, dtype) in zip(grads, ctx.meta)))
+
+
+def _partials(b: int, per_row: int, dev) -> Optional[torch.Tensor]:
+    """The f64 scratch of a loss kernel with ``per_row`` sums over ``b`` rows (csrc/loss_sum.h):
+    None while one workgroup covers the batch."""
+    nparts = int(_C.lib().tsrl_ddpg_num_partials(b))
+    return torch.empty(per_row * nparts, dtype=torch.float64, device=dev) if nparts > 1 else None
 
 
 def replay_learn_graph(cache: Dict[tuple, dict], key: tuple, addr: tuple, inputs: Sequence,

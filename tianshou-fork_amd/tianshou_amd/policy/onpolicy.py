@@ -27,7 +27,7 @@ from tianshou_amd.data.batch import Batch, gather_rows
 from tianshou_amd.dist import LOG
 from tianshou_amd.utils.capture import graph_capture
 from tianshou_amd.policy.flat_adam import FlatAdam
-from tianshou_amd.policy.flat_learn import flat_backward
+from tianshou_amd.policy.flat_learn import _is_unit_seed, _unit_seed, flat_backward
 from tianshou_amd.utils.np_perm import LegacyPermutation
 
 # a shared uint8 conv trunk reads each minibatch's frame stacks in place from the whole batch
@@ -156,24 +156,6 @@ class _CatPPOLoss(torch.autograd.Function):
             # loss.backward(UNIT): the gradients are the kernel's as they are (x * 1.0 is x)
             return grad_x, grad_value, None
         return grad_x * g_loss, grad_value * g_loss, None
-
-
-_UNIT = {}
-
-
-def _unit_seed(dev: torch.device) -> torch.Tensor:
-    """A constant f32 1.0 on dev, the seed gradient of the Categorical minibatch's
-    loss.backward(): it spares autograd's ones_like fill, and _CatPPOLoss recognises it and
-    skips two scaling passes (round 6).  Never written."""
-    t = _UNIT.get(dev)
-    if t is None:
-        t = _UNIT[dev] = torch.ones((), dtype=torch.float32, device=dev)
-    return t
-
-
-def _is_unit_seed(g: torch.Tensor) -> bool:
-    t = _UNIT.get(g.device)
-    return t is not None and g.dim() == 0 and g.data_ptr() == t.data_ptr()
 
 
 class FusedLearnMixin:

@@ -37,8 +37,8 @@ import torch
 from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
 from tianshou_amd.exploration import BaseNoise
-from tianshou_amd.policy.ddpg import DDPGPolicy, _partials
-from tianshou_amd.policy.onpolicy import _is_unit_seed
+from tianshou_amd.policy.ddpg import DDPGPolicy
+from tianshou_amd.policy.flat_learn import KernelGradLoss, _partials
 from tianshou_amd.policy.sac import _rows, _SquashedGaussianMixin, sac_sample
 
 TARGET_MODES = {"min": 0, "mean": 1}
@@ -68,7 +68,7 @@ def redq_target_device(qs: torch.Tensor, idx: np.ndarray, mode: str, log_prob: t
     return out.view(b, 1)
 
 
-class _RedqQLoss(torch.autograd.Function):
+class _RedqQLoss(KernelGradLoss):
     """redq.py:161-169 as tsrl_redq_q_loss_fwd_bwd.  The output is the handle to call backward
     on; the loss and the per-row mean TD error go to ``loss`` / ``td`` (see redq_q_loss)."""
 
@@ -88,16 +88,8 @@ class _RedqQLoss(torch.autograd.Function):
             _C.ptr(x), _C.ptr(returns, torch.float32), _C.ptr(weight, torch.float32), E, b,
             _C.ptr(grad), _C.ptr(td, torch.float32), _C.ptr(_partials(b, 1, dev)),
             _C.ptr(loss, torch.float32), _C.stream_ptr(dev)), "tsrl_redq_q_loss_fwd_bwd")
-        ctx.save_for_backward(grad)
-        ctx.q_dtype = q.dtype
+        KernelGradLoss.keep(ctx, (grad,), (q,))
         return torch.empty((), dtype=torch.float32, device=dev)
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        if not _is_unit_seed(g):  # backward(UNIT): the kernel's gradient as it is
-            grad = grad * g
-        return None, grad.to(ctx.q_dtype)
 
 
 def redq_q_loss(q: torch.Tensor, returns: torch.Tensor, weight: Optional[torch.Tensor],
@@ -111,7 +103,7 @@ def redq_q_loss(q: torch.Tensor, returns: torch.Tensor, weight: Optional[torch.T
     return _RedqQLoss.apply((returns, weight, td, loss), q), loss, td
 
 
-class _RedqActorLoss(torch.autograd.Function):
+class _RedqActorLoss(KernelGradLoss):
     """redq.py:176-189 as tsrl_redq_actor_loss_fwd_bwd.  The output is the handle to call
     backward on (towards q and log_prob); the losses go to ``loss`` and the temperature's
     gradient to ``g_log_alpha`` (see redq_actor_loss)."""
@@ -134,16 +126,8 @@ class _RedqActorLoss(torch.autograd.Function):
             _C.ptr(glp), _C.ptr(_partials(b, 2, dev)), _C.ptr(loss, torch.float32),
             _C.ptr(g_log_alpha, torch.float32), _C.stream_ptr(dev)),
             "tsrl_redq_actor_loss_fwd_bwd")
-        ctx.save_for_backward(gq, glp)
-        ctx.meta = [(t.shape, t.dtype) for t in (q, log_prob)]
+        KernelGradLoss.keep(ctx, (gq, glp), (q, log_prob))
         return torch.empty((), dtype=torch.float32, device=dev)
-
-    @staticmethod
-    def backward(ctx, g):
-        grads = ctx.saved_tensors
-        if not _is_unit_seed(g):
-            grads = [t * g for t in grads]
-        return (None, *(t.view(shape).to(dtype) for t, (shape, dtype) in zip(grads, ctx.meta)))
 
 
 def redq_actor_loss(q: torch.Tensor, log_prob: torch.Tensor, alpha: torch.Tensor,

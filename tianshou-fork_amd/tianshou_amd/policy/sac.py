@@ -34,9 +34,9 @@ from torch.distributions import Independent, Normal
 from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
 from tianshou_amd.exploration import BaseNoise
-from tianshou_amd.policy.ddpg import DDPGPolicy, _partials, q_mse_loss
+from tianshou_amd.policy.ddpg import DDPGPolicy, q_mse_loss
 from tianshou_amd.policy.flat_adam import FlatAdam
-from tianshou_amd.policy.onpolicy import _is_unit_seed
+from tianshou_amd.policy.flat_learn import KernelGradLoss, _partials
 
 EPS32 = np.finfo(np.float32).eps.item()
 
@@ -107,7 +107,7 @@ def sac_target_device(q1: torch.Tensor, q2: torch.Tensor, log_prob: torch.Tensor
     return out.view(q1.shape)
 
 
-class _SacActorLoss(torch.autograd.Function):
+class _SacActorLoss(KernelGradLoss):
     """sac.py:162-165 and 171-173 as tsrl_sac_actor_loss_fwd_bwd.  The output is the handle to
     call backward on (towards q1, q2 and log_prob); the losses go to ``loss`` and the
     temperature's gradient to ``g_log_alpha`` (see sac_actor_loss)."""
@@ -128,16 +128,8 @@ class _SacActorLoss(torch.autograd.Function):
             *(_C.ptr(t) for t in grads), _C.ptr(_partials(b, 2, dev)),
             _C.ptr(loss, torch.float32), _C.ptr(g_log_alpha, torch.float32),
             _C.stream_ptr(dev)), "tsrl_sac_actor_loss_fwd_bwd")
-        ctx.save_for_backward(*grads)
-        ctx.meta = [(t.shape, t.dtype) for t in (q1, q2, log_prob)]
+        KernelGradLoss.keep(ctx, grads, (q1, q2, log_prob))
         return torch.empty((), dtype=torch.float32, device=dev)
-
-    @staticmethod
-    def backward(ctx, g):
-        grads = ctx.saved_tensors
-        if not _is_unit_seed(g):
-            grads = [t * g for t in grads]
-        return (None, *(t.view(shape).to(dtype) for t, (shape, dtype) in zip(grads, ctx.meta)))
 
 
 def sac_actor_loss(q1: torch.Tensor, q2: torch.Tensor, log_prob: torch.Tensor,
