@@ -384,3 +384,54 @@ def test_other_rmsprop_falls_back_to_torch(golden_dir, dev, variant):
     for k, a in runs[1][1].items():
         np.testing.assert_allclose(runs[0][1][k], a, rtol=1e-5, atol=1e-4, err_msg=k)
 
+
+
+# -- masked and wide Categorical policies (tests/loss_edges_common.py) --------------------------
+def test_learn_masked_actor_matches_generic(dev):
+    """An actor that writes -inf over illegal actions, A2CPolicy.learn on the fused Categorical
+    path against a twin with the same weights and seed on _learn_generic: every parameter
+    finite, losses and parameters at tests/test_gpu_ppo_discrete.py's
+    test_learn_discrete_matches_reference tolerances."""
+    from tianshou_amd.policy import A2CPolicy
+    from tests import loss_edges_common as lc
+    policy, twin = lc.discrete_policy(A2CPolicy, dev, lambda: lc.MaskedActor(dev), 6, seed=41)
+    assert policy._cat == 0 and not policy._fused
+    batch = lc.discrete_batch(policy, dev, 200, 6, seed=42, illegal=lc.MASKED_ACTIONS)
+    fused = lc.count_calls(policy, "_learn_cat")
+    np.random.seed(21)
+    res = policy.learn(batch, batch_size=64, repeat=2)
+    assert fused == ["_learn_cat"]
+    np.random.seed(21)
+    res_twin = twin._learn_generic(batch, 64, 2)
+    print("masked A2C losses:", res["loss"])
+    lc.compare_runs(res, res_twin, lc.state_of(policy), lc.state_of(twin), common.KEYS,
+                    (1e-4, 1e-5), (1e-5, 1e-6), "masked A2C")
+
+
+@pytest.mark.parametrize("n_act", [65, 100])
+def test_wide_categorical_policy(dev, n_act):
+    """More actions than the loss kernels take: A2CPolicy's process_fn and learn() run the
+    generic loop, bit for bit the twin's forced onto it."""
+    from tianshou_amd.policy import A2CPolicy
+    from tianshou_amd.utils.net import DiscreteActor, Net
+    from tests import loss_edges_common as lc
+    make = lambda: DiscreteActor(Net(8, hidden_sizes=(64, 64), device=dev), n_act,  # noqa: E731
+                                 softmax_output=False, device=dev)
+    policy, twin = lc.discrete_policy(A2CPolicy, dev, make, n_act, seed=43)
+    runs = []
+    for pol in (policy, twin):
+        buf = lc.filled_buffer(dev, 8, 25, 8, lambda rng, E: rng.randint(0, n_act, E), seed=44)
+        batch, idx = buf.sample(0)
+        batch = pol.process_fn(batch, buf, idx)
+        generic, fused = lc.count_calls(pol, "_learn_generic"), lc.count_calls(pol, "_learn_cat")
+        np.random.seed(21)
+        if pol is policy:
+            res = pol.learn(batch, batch_size=64, repeat=2)
+            assert (len(generic), len(fused)) == (1, 0)
+        else:
+            res = pol._learn_generic(batch, 64, 2)
+        assert all(np.isfinite(res[k]).all() for k in res)
+        runs.append((res, lc.state_of(pol)))
+    assert runs[0][0] == runs[1][0]  # bit for bit
+    for k, v in runs[0][1].items():
+        assert torch.equal(v, runs[1][1][k]), k

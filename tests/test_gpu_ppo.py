@@ -204,3 +204,55 @@ def test_learn_matches_reference(golden_dir, dev, tag):
             # measured (round 3): <= 5.7e-7 abs after the Adam steps (parameters ~0.1)
             np.testing.assert_allclose(sd[k[len(p + "final_"):]].cpu().numpy(), z[k],
                                        rtol=1e-5, atol=2e-6)
+
+
+@pytest.mark.parametrize("A", [33, 64, 65])
+def test_wide_gaussian_policy(dev, A):
+    """get_actor_critic with more action dimensions than the fused MLP takes (32): 33 and 64
+    use the fused loss kernel over the torch layers and match a twin on _learn_generic at
+    test_learn_matches_reference's tolerances; 65 is wider than the loss kernels too, and
+    process_fn and learn() fall back to the generic loop (bit for bit the twin)."""
+    import copy
+    from tianshou_amd.data import Batch
+    from tianshou_amd.env import Box
+    from tianshou_amd.policy import PPOPolicy
+    from tianshou_amd.utils.models import fixed_std_normal, get_actor_critic, init_and_get_optim
+    from . import loss_edges_common as lc
+    torch.manual_seed(50 + A)
+    actor, critic = get_actor_critic((17,), (64, 64), (A,), dev)
+    pols = []
+    for a, c in ((actor, critic), (copy.deepcopy(actor), copy.deepcopy(critic))):
+        optim = init_and_get_optim(a, c, 3e-4)
+        pols.append(PPOPolicy(a, c, optim, fixed_std_normal, action_space=Box(-1.0, 1.0, (A,)),
+                              max_grad_norm=0.5, vf_coef=0.25, ent_coef=0.0).to(dev))
+    pols[1].load_state_dict(pols[0].state_dict())
+    policy, twin = pols
+    assert policy._fused and policy._mlp is None
+    n = 256
+    g = torch.Generator().manual_seed(60 + A)
+    obs = torch.randn(n, 17, generator=g).to(dev)
+    with torch.no_grad():
+        mu = policy.actor.forward_mu(obs)
+        sigma = policy.actor.sigma_param.view(1, -1).exp().expand_as(mu)
+        act = mu + sigma * torch.randn(n, A, generator=g).to(dev)
+        lp = fixed_std_normal(mu, sigma).log_prob(act)
+    ret = torch.randn(n, generator=g)
+    batch = Batch(obs=obs, act=act, adv=torch.randn(n, generator=g).to(dev), returns=ret.to(dev),
+                  v_s=(ret + 0.3 * torch.randn(n, generator=g)).to(dev))
+    got = policy._logp_old(batch)  # tsrl_gauss_logp up to 64 dimensions, torch's above
+    np.testing.assert_allclose(got.cpu().numpy(), lp.cpu().numpy(), rtol=1e-5, atol=1e-5)
+    batch.logp_old = lp + 0.1 * torch.randn(n, generator=g).to(dev)
+    generic = lc.count_calls(policy, "_learn_generic")
+    np.random.seed(21)
+    res = policy.learn(batch, batch_size=64, repeat=2)
+    assert len(generic) == (1 if A > 64 else 0)
+    np.random.seed(21)
+    res_twin = twin._learn_generic(batch, 64, 2)
+    keys = ("loss", "loss/clip", "loss/vf", "loss/ent")
+    if A > 64:
+        assert res == res_twin  # bit for bit: the same code
+        for k, v in lc.state_of(policy).items():
+            assert torch.equal(v, lc.state_of(twin)[k]), k
+    else:
+        lc.compare_runs(res, res_twin, lc.state_of(policy), lc.state_of(twin), keys,
+                        (2e-5, 1e-6), (1e-5, 2e-6), f"Gaussian A={A}")

@@ -238,3 +238,69 @@ def test_learn_discrete_matches_reference(golden_dir, dev, tag):
             # measured (round 3): <= 2.1e-7 abs after the Adam steps (round 2: 1e-3 / 1e-5)
             np.testing.assert_allclose(sd[k[len(p + "final_"):]].cpu().numpy(), z[k],
                                        rtol=1e-5, atol=1e-6)
+
+
+# -- masked and wide Categorical policies (tests/loss_edges_common.py) --------------------------
+def test_learn_masked_actor_matches_generic(dev):
+    """An actor that writes -inf over illegal actions, PPOPolicy.learn on the fused Categorical
+    path (eager first epoch, graph replay after it) against a twin with the same weights and
+    seed on _learn_generic: every parameter finite, losses and parameters at
+    test_learn_discrete_matches_reference's tolerances."""
+    from tianshou_amd.policy import PPOPolicy
+    from . import loss_edges_common as lc
+    policy, twin = lc.discrete_policy(PPOPolicy, dev, lambda: lc.MaskedActor(dev), 6, seed=31)
+    assert policy._cat == 0 and not policy._fused
+    batch = lc.discrete_batch(policy, dev, 200, 6, seed=32, illegal=lc.MASKED_ACTIONS)
+    with torch.no_grad():
+        x = policy.actor(batch.obs)[0]
+    assert bool(torch.isinf(x).any()) and bool(torch.isfinite(x[torch.arange(200), batch.act]).all())
+    fused = lc.count_calls(policy, "_learn_cat")
+    np.random.seed(21)
+    res = policy.learn(batch, batch_size=64, repeat=2)
+    assert fused == ["_learn_cat"]
+    np.random.seed(21)
+    res_twin = twin._learn_generic(batch, 64, 2)
+    print("masked PPO losses:", res["loss"])
+    lc.compare_runs(res, res_twin, lc.state_of(policy), lc.state_of(twin),
+                    ("loss", "loss/clip", "loss/vf", "loss/ent"), (1e-4, 1e-5), (1e-5, 1e-6),
+                    "masked PPO")
+
+
+@pytest.mark.parametrize("n_act", [64, 65, 100])
+def test_wide_categorical_policy(dev, n_act):
+    """More actions than the loss kernels take (64): process_fn and learn() run the torch
+    formulation, bit for bit the twin's forced onto _learn_generic (the same code); 64 actions
+    still take the fused path."""
+    from tianshou_amd.policy import PPOPolicy
+    from tianshou_amd.utils.net import DiscreteActor, Net
+    from . import loss_edges_common as lc
+    make = lambda: DiscreteActor(Net(8, hidden_sizes=(64, 64), device=dev), n_act,  # noqa: E731
+                                 softmax_output=False, device=dev)
+    policy, twin = lc.discrete_policy(PPOPolicy, dev, make, n_act, seed=33)
+    assert policy._cat == 0
+    runs = []
+    for pol in (policy, twin):
+        buf = lc.filled_buffer(dev, 8, 25, 8, lambda rng, E: rng.randint(0, n_act, E), seed=34)
+        batch, idx = buf.sample(0)
+        batch = pol.process_fn(batch, buf, idx)
+        with torch.no_grad():
+            lp = lc.cat_logits(pol.actor(batch.obs)[0]).log_prob(batch.act)
+        np.testing.assert_allclose(batch.logp_old.cpu().numpy(), lp.cpu().numpy(), rtol=1e-5,
+                                   atol=1e-6)
+        generic, fused = lc.count_calls(pol, "_learn_generic"), lc.count_calls(pol, "_learn_cat")
+        np.random.seed(21)
+        if pol is policy:
+            res = pol.learn(batch, batch_size=64, repeat=2)
+            assert (len(generic), len(fused)) == ((0, 1) if n_act <= 64 else (1, 0))
+        else:
+            res = pol._learn_generic(batch, 64, 2)
+        assert all(np.isfinite(res[k]).all() for k in res)
+        runs.append((res, lc.state_of(pol)))
+    if n_act > 64:
+        assert runs[0][0] == runs[1][0]  # bit for bit
+        for k, v in runs[0][1].items():
+            assert torch.equal(v, runs[1][1][k]), k
+    else:
+        lc.compare_runs(runs[0][0], runs[1][0], runs[0][1], runs[1][1],
+                        ("loss", "loss/clip", "loss/vf", "loss/ent"), (1e-4, 1e-5), (1e-5, 1e-6),
+                        "64 actions")

@@ -149,11 +149,14 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
     if (live) {
         float an = adv[j];
         if (p.norm_adv) an = (an - mean_f) / (std_f + p.adv_eps);
-        float logp = 0.0f;
+        // the f32 terms summed in f64 and rounded once: an f32 running sum over 64 terms loses
+        // ~5x the accuracy of torch's sum(-1), which the ratio exp(logp - logp_old) then shows
+        double lp = 0.0;
         for (int64_t a = 0; a < A; ++a) {
             const float diff = my_act[a] - my_mu[a];
-            logp += gauss_logp_term(diff, s_var[a], s_ls[a]);
+            lp += (double)gauss_logp_term(diff, s_var[a], s_ls[a]);
         }
+        const float logp = (float)lp;
         const PolicyTerm pt =
             policy_term(logp, p.objective == OBJ_A2C ? 0.0f : logp_old[j], an, p);
         clip_term = -(double)pt.obj;
@@ -197,7 +200,8 @@ __global__ __launch_bounds__(TPB) void gauss_fwd_bwd_kernel(
 
 __global__ void gauss_finalize_kernel(const double* sums, int A, const float* log_std,
                                       LossParams p, float* losses, float* grad_log_std) {
-    gauss_finalize(sums, A, log_std, p.vf_coef, p.ent_coef, p.inv_b, losses, grad_log_std);
+    gauss_finalize<double>(sums, A, log_std, p.vf_coef, p.ent_coef, p.inv_b, losses,
+                           grad_log_std);
 }
 
 __global__ __launch_bounds__(TPB) void gauss_logp_kernel(const float* mu, const float* log_std,
@@ -212,12 +216,12 @@ __global__ __launch_bounds__(TPB) void gauss_logp_kernel(const float* mu, const 
     __syncthreads();
     for (int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x; r < b;
          r += (int64_t)gridDim.x * TPB) {
-        float lp = 0.0f;
+        double lp = 0.0;  // as gauss_fwd_bwd_kernel: the same bits, so an unchanged policy has ratio 1
         for (int64_t a = 0; a < A; ++a) {
             const float diff = act[r * A + a] - mu[r * A + a];
-            lp += gauss_logp_term(diff, s_var[a], s_ls[a]);
+            lp += (double)gauss_logp_term(diff, s_var[a], s_ls[a]);
         }
-        out[r] = lp;
+        out[r] = (float)lp;
     }
 }
 

@@ -10,6 +10,13 @@
 // logits = log(clamp(probs, eps, 1 - eps)); log_prob = logits[a]; entropy =
 // -sum(clamp(logits, min=f32 min) * probs)), and its backward is written out: on ties min/max
 // split the gradient in half and clamp passes it on the closed interval, as torch does.
+// -inf logits (mode 0: masked, illegal actions) are in scope and follow torch: a masked entry
+// has probability 0, contributes 0 to the entropy (the clamp at f32 min, in the forward and in
+// the gradient alike) and gets gradient exactly 0; a row whose taken action is masked has
+// log_prob -inf and ratio 0.  A row of all -inf is NaN (loss and gradient), as in torch.
+// Accepted widths: 1 <= nA <= MAX_ACT = 64; the loss kernel stages 2 * 256 * nA floats of
+// dynamic LDS per workgroup (2 KiB * nA: 128 KiB at nA = 64).  Wider inputs are an argument
+// error; the Python layer takes the torch path for them (policy/fused_mlp.py LOSS_MAX_ACT).
 // One workgroup = 256 minibatch rows; the [256, nA] tile of x (contiguous, minibatch order)
 // is staged in LDS, the gathered rows of act/logp_old/adv/returns/v_s come through idx.
 #include "ppo_loss.h"
@@ -64,9 +71,11 @@ __device__ __forceinline__ Row cat_row(float* x, float* l, int A, int mode, uint
             l[j] = logf(qc);
         }
     }
-    float h = 0.0f;
-    for (int j = 0; j < A; ++j) h += fmaxf(l[j], F32_MIN) * x[j];
-    o.H = -h;
+    // the f32 products summed in f64 and rounded once (a single row of 32 actions showed an
+    // f32 running sum 2.7 ulp off, where torch's sum(-1) is within one)
+    double h = 0.0;
+    for (int j = 0; j < A; ++j) h += (double)(fmaxf(l[j], F32_MIN) * x[j]);
+    o.H = (float)(-h);
     return o;
 }
 
@@ -114,7 +123,10 @@ __global__ __launch_bounds__(TPB) void cat_fwd_bwd_kernel(
         if (mode == 0) {
             for (int k = 0; k < A; ++k) {
                 const float qk = q[k];
-                const float g = c_lp * ((k == a ? 1.0f : 0.0f) - qk) + c_h * (-qk * (l[k] + row.H));
+                // the clamped logit, as in the entropy above: a masked entry (l = -inf, q = 0)
+                // gets gradient 0, not 0 * inf
+                const float g = c_lp * ((k == a ? 1.0f : 0.0f) - qk) +
+                                c_h * (-qk * (fmaxf(l[k], F32_MIN) + row.H));
                 l[k] = g;
             }
             for (int k = 0; k < A; ++k) q[k] = l[k];

@@ -169,16 +169,21 @@ __device__ __forceinline__ ValueLoss value_loss(float v, float ret, float v_s,
 
 // Loss terms (thread 0: loss, clip, vf, entropy) and the log-std gradient (strided over the
 // block) of the Gaussian policy from the reduced sums [4 + A] = clip, vf, count, 0,
-// d/dlog_std[A].  Every thread of the block calls it.
+// d/dlog_std[A].  Every thread of the block calls it.  Acc is the type the per-dimension
+// entropies are summed in: float is ppo_tail16_kernel's contract (at most 32 dimensions);
+// gauss_finalize_kernel, which takes up to 64, sums in double and rounds once (an f32 running
+// sum over 63 terms was off by 3.6 ulp, more than torch's sum(-1) ever is).
+template <typename Acc = float>
 __device__ __forceinline__ void gauss_finalize(const double* sums, int A, const float* log_std,
                                                float vf_coef, float ent_coef, double inv_b,
                                                float* losses, float* grad_log_std) {
     if (threadIdx.x == 0) {
-        float ent = 0.0f;
+        Acc ent_sum = 0;
         for (int a = 0; a < A; ++a) {
             const float sig = expf(log_std[a]);
-            ent += 1.4189385332046727f + logf(sig);  // f32(0.5 + 0.5*log(2*pi)) + log(scale)
+            ent_sum += 1.4189385332046727f + logf(sig);  // f32(0.5 + 0.5*log(2*pi)) + log(scale)
         }
+        const float ent = (float)ent_sum;
         const float clip = (float)(sums[0] * inv_b);
         const float vf = (float)(sums[1] * inv_b);
         losses[0] = clip + vf_coef * vf - ent_coef * ent;

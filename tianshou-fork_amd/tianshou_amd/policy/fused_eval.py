@@ -78,13 +78,38 @@ class FusedEvalMixin:
             if layers is not None:
                 self._mlp = _fmlp.FusedActorCritic(layers, self._actor_critic.parameters())
 
+    def _loss_width(self) -> Optional[int]:
+        """The action dimension (Gaussian) or action count (Categorical) the actor emits, as
+        far as it is known without a forward pass: the actor's ``output_dim``, else a Discrete
+        action space's ``n``; None when neither says."""
+        w = getattr(self.actor, "output_dim", None)
+        if w is None and self._cat is not None:
+            w = getattr(getattr(self, "action_space", None), "n", None)
+        return None if w is None else int(w)
+
+    def _loss_kernels_ok(self, width: Optional[int] = None) -> bool:
+        """Whether the loss / log-prob kernels take this width (at most
+        ``fused_mlp.LOSS_MAX_ACT``); wider policies run the torch formulation.  An unknown
+        width goes to the kernels, whose argument check speaks for itself."""
+        if width is None:
+            width = self._loss_width()
+        return width is None or width <= _fmlp.LOSS_MAX_ACT
+
+    def _cat_logp_rows(self, x: torch.Tensor, act: torch.Tensor) -> torch.Tensor:
+        """log pi(act|.) of actor output rows x: tsrl_cat_logp, or dist_fn's own log_prob
+        above the kernel's width."""
+        if not self._loss_kernels_ok(x.shape[-1]):
+            from tianshou_amd.policy.pg import make_dist
+            return make_dist(self.dist_fn, x, self.validate_args).log_prob(act).float()
+        return cat_logp(x, act, self._cat)
+
     def _logp_old(self, batch) -> torch.Tensor:
         """log pi_old(act|obs) of every row (after _compute_returns, which may have produced
         it already on the fused path)."""
         with torch.no_grad():
             if self._pending_logp is not None:
                 out = self._pending_logp
-            elif self._fused:
+            elif self._fused and self._loss_kernels_ok():
                 out = self._logp_fused(batch.obs, batch.act)
             elif self._cat is not None and isinstance(batch.obs, torch.Tensor) and \
                     batch.obs.is_cuda:
@@ -144,6 +169,11 @@ class FusedEvalMixin:
         log_std = self.actor.sigma_param.detach().reshape(-1).contiguous()
         L = _C.lib()
         for s, e in self._chunks(n):
+            if not self._loss_kernels_ok(A):  # wider than tsrl_gauss_logp takes: torch's
+                from tianshou_amd.policy.pg import make_dist
+                out[s:e] = make_dist(self.dist_fn, self.actor(obs[s:e])[0],
+                                     self.validate_args).log_prob(act[s:e])
+                continue
             mu = self.actor.forward_mu(obs[s:e]).contiguous()
             _C.check(L.tsrl_gauss_logp(_C.ptr(mu), _C.ptr(log_std), _C.ptr(act[s:e]), e - s, A,
                                        _C.ptr(out[s:e]), _C.stream_ptr(dev)), "tsrl_gauss_logp")
@@ -178,7 +208,7 @@ class FusedEvalMixin:
             x, v = self._trunk_heads(obs[s:e])
             v_s[s:e] = v
             if self._needs_logp:
-                logp[s:e] = cat_logp(x, act[s:e], self._cat)
+                logp[s:e] = self._cat_logp_rows(x, act[s:e])
         self._pending_logp = logp if self._needs_logp else None
         p = self._next_positions(buffer, indices, dev)
         return v_s, (v_s[p] if p is not None else self._values(obs_next))
@@ -189,6 +219,6 @@ class FusedEvalMixin:
         act = torch.as_tensor(act, device=obs.device).reshape(n)
         for s, e in self._chunks(n, obs[0].numel() if n else 1):
             x, _ = self.actor(obs[s:e])
-            out[s:e] = cat_logp(x, act[s:e], self._cat)
+            out[s:e] = self._cat_logp_rows(x, act[s:e])
         return out
 

@@ -25,6 +25,9 @@ from tianshou_amd.policy.flat_adam import FlatAdam
 
 HIDDEN = 64
 MAX_ACT = 32
+# widest action dimension / action count the loss and log-prob kernels accept (MAX_ACT of
+# csrc/ppo.hip and csrc/ppo_cat.hip); wider policies take the torch formulation
+LOSS_MAX_ACT = 64
 # first-layer forward on the bf16 matrix cores with the exact 3-way operand split
 # (tsrl_mlp_l1_fwd_x6, f32-level error); False: the f32-input MFMA kernel (tsrl_mlp_l1_fwd)
 L1_X6 = True

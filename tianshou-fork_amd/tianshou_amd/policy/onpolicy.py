@@ -265,7 +265,8 @@ class FusedLearnMixin:
         return out
 
     def _learn(self, batch: Batch, batch_size: int, repeat: int) -> Dict[str, List[float]]:
-        if not self._fused_learn_ok(batch):
+        if not self._fused_learn_ok(batch) or not self._loss_kernels_ok():
+            # (wider than the loss kernels take, fused_mlp.LOSS_MAX_ACT: the torch loop)
             return self._learn_generic(batch, batch_size, repeat)
         if not self._fused:
             if self._cat is not None and isinstance(batch.obs, torch.Tensor) and \
@@ -576,7 +577,10 @@ class FusedLearnMixin:
         plain Adam the gradients live in one flat bucket and clip_grad_norm_ + Adam.step() are
         one HIP pass (policy/flat_adam.py); epochs after the first eager one then replay from
         a captured HIP graph (small minibatches -- test_ppo.py's 64 rows -- are otherwise
-        bound by ~40 host launches each)."""
+        bound by ~40 host launches each).  More actions than the kernel takes
+        (fused_mlp.LOSS_MAX_ACT): the generic loop."""
+        if not self._loss_kernels_ok():
+            return self._learn_generic(batch, batch_size, repeat)
         dev = batch.returns.device
         n = len(batch.returns)
         terms = []
