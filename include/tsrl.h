@@ -871,17 +871,22 @@ int tsrl_eps_greedy(int64_t* act, const double* u_row, const double* u_act,
  *   1) * next[r][j]; ce[r] = -sum_i t_i log(curr[r][act[r]][i] + 1e-8); *loss = mean(ce *
  *   weight) (weight NULL: 1); grad[b, num_actions, n] = d(loss)/d(curr), written in full (zero
  *   off the taken action).  The projected target stays in registers; all arithmetic is f64 on
- *   the f32 inputs.  2 <= n <= 4096.
+ *   the f32 inputs.  2 <= n <= TSRL_DIST_MAX_N.
  * tsrl_qr_loss_fwd_bwd: learn() (qrdqn.py:82-93).  With u_ij = returns[r][j] -
  *   curr[r][act[r]][i], h = smooth_l1(u) at beta 1 and k_ij = |tau_hat[i] - 1{u_ij <= 0}|:
  *   huber_r = (1/n) sum_ij h_ij k_ij, prio[r] = (1/n) sum_ij h_ij, *loss = mean(huber *
  *   weight), grad[r][act[r]][i] = -(weight[r] / (b n)) sum_j clamp(u_ij, -1, 1) k_ij (the
- *   indicator carries no gradient, as in the reference), zero elsewhere.  1 <= n <= 4096.
+ *   indicator carries no gradient, as in the reference), zero elsewhere.  1 <= n <=
+ *   TSRL_DIST_MAX_N.
  * Both losses: an action outside [0, num_actions) gives a NaN ce / prio and loss and an
  *   all-zero gradient row.  The loss is an f64 sum in a fixed order (lanes, waves, then the
  *   rows by a second one-wave launch when b > 1): bit-identical between runs.  partials: b
- *   doubles, may be NULL when b == 1.
+ *   doubles, may be NULL when b == 1.  A wider n is an argument error: nothing is launched or
+ *   written.  Non-finite inputs follow torch: a NaN return (or a NaN in next) makes that row's
+ *   ce / prio, its gradient row and the loss NaN and touches no other row; C51 clamps a +-inf
+ *   return to the support's ends, QR gives an infinite loss and priority.
  * ------------------------------------------------------------------------------- */
+#define TSRL_DIST_MAX_N 4096
 int tsrl_dist_select(const float* sel, const float* eval, const float* w, int64_t b,
                      int64_t num_actions, int64_t n, float* q_out, int64_t* act_out,
                      float* row_out, void* stream);

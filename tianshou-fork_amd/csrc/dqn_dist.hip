@@ -17,7 +17,7 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int NW = TPB / kWave;
-constexpr int64_t kMaxN = 4096;  // the loss kernels stage up to 2 N floats in LDS (32 KiB)
+constexpr int64_t kMaxN = TSRL_DIST_MAX_N;  // the loss kernels stage 2 N floats in LDS (32 KiB)
 
 // (v, a) replaces (best, arg) as the row's argmax: torch's rule (the first index of the
 // maximum, the first NaN beats everything), for candidates met in any order.
@@ -140,8 +140,12 @@ __global__ __launch_bounds__(TPB) void c51_loss_kernel(
     }
     for (int64_t j = t; j < N; j += blockDim.x) {
         const float x = returns[r * N + j];
-        s_tz[j] = x != x ? x : fminf(fmaxf(x, v_min), v_max);  // torch's clamp keeps a NaN
-        s_p[j] = next[r * N + j];
+        const bool nan = x != x;
+        s_tz[j] = nan ? x : fminf(fmaxf(x, v_min), v_max);  // torch's clamp keeps a NaN
+        // ... and so does its clamp(0, 1) of the projection weight: a NaN return's weight
+        // towards every atom is NaN, and with it every t_i of the row, whatever next holds
+        // there.  The fmin / fmax below drop a NaN, so it travels in the staged probability.
+        s_p[j] = nan ? x : next[r * N + j];
     }
     __syncthreads();
     const double wr = weight ? (double)weight[r] : 1.0;
@@ -208,6 +212,17 @@ __global__ __launch_bounds__(TPB) void qr_loss_kernel(
             hi += h * k;
             pri += h;
             g += fmin(fmax(u, -1.0), 1.0) * k;
+        }
+        if (hi != hi) {
+            // Some u_ij is NaN (a NaN target or quantile, inf - inf): h is NaN there, but fmin /
+            // fmax above made the derivative -1.  torch's smooth_l1 backward keeps the NaN, so
+            // this quantile's sum is taken again with it kept.  (hi is also NaN at inf * 0, a
+            // tau_hat of exactly 0 or 1; the second pass then gives what the first one gave.)
+            g = 0.0;
+            for (int64_t j = 0; j < N; ++j) {
+                const double u = (double)lds[j] - th;
+                g += (u != u ? u : fmin(fmax(u, -1.0), 1.0)) * (u <= 0.0 ? k_neg : k_pos);
+            }
         }
         hub += hi;
         g_row[a * N + i] = (float)(-g * gscale);

@@ -10,7 +10,10 @@
 // Per row, in f64 on the f32 inputs: m = max_j l_j, S = sum_j exp(l_j - m), lp_j = l_j - m -
 // log S, p_j = exp(lp_j), H = -sum_j p_j lp_j (a term with p_j == 0 is exactly 0), qm_j =
 // min(q1_j, q2_j) (a NaN handed through), V = sum_j p_j qm_j: what Categorical(logits=l)
-// normalises to for finite logits.  A -inf logit is out of scope (lp_j = -inf, p_j lp_j = NaN).
+// normalises to.  A -inf logit (an illegal action masked out by the actor) follows torch: p_j = 0,
+// nothing added to H or V (0 * a finite q), and in the actor loss a gradient of exactly 0, through
+// the clamp of lp_j at f32's lowest value that torch's entropy() applies.  A row of all -inf, a
+// +inf or a NaN logit make that row's outputs and the losses NaN, as in torch, and no other row's.
 //
 // Row mapping: a group of G lanes shares one row, G = the power of two >= A capped at one wave
 // (A = 1: 1, A = 18: 32, A > 64: 64 with a loop), lane g of the group on columns g, g + G, ...
@@ -23,6 +26,7 @@ namespace tsrl {
 namespace {
 
 constexpr int TPB = kLossTPB;
+constexpr double kF32Min = -3.4028234663852886e+38;  // torch.finfo(torch.float32).min
 
 // Butterflies over the G lanes of a group: every lane ends with the same bits (each level adds
 // or compares the same two values on both sides).
@@ -174,7 +178,11 @@ __global__ __launch_bounds__(TPB) void dsac_actor_loss_kernel(
                 const double lp = (double)l[j] - st.shift;
                 const double p = exp(lp);
                 const double adv = (double)min_nan(q1[o + j], q2[o + j]) - st.V;
-                const double ent = al * (lp + st.H);
+                // torch's entropy() clamps the normalised logit at f32's lowest value: a -inf
+                // (masked) entry has p = 0 and a finite ent, so its gradient is 0 * finite = 0
+                // and not 0 * inf.  Every lp above that value is left as it is, and below it p
+                // is 0 already; a NaN lp has a NaN p.
+                const double ent = al * (fmax(lp, kF32Min) + st.H);
                 g_logits[o + j] = (float)(-inv_b * (p * (adv - ent)));
             }
         }

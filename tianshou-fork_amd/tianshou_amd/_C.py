@@ -268,6 +268,7 @@ _SIGS = {
 NOISY_DESC_WORDS = 10
 DUELING_MAX_ROW = 4096        # TSRL_DUELING_MAX_ROW
 ERR_DUELING_ROW = 100001      # TSRL_ERR_DUELING_ROW
+DIST_MAX_N = 4096             # TSRL_DIST_MAX_N: atoms / quantiles the C51 and QR loss kernels take
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

@@ -9,7 +9,7 @@ distribution (c51.py:82-89) inside the loss kernel instead of building the refer
 the weights of this very update, ``obs_next`` is one more static input of the learn graph: the
 graph holds the no-grad forwards on obs_next, the select launch, the forward on obs, the loss,
 the backward and the flat optimiser pass.  ``fused = False`` runs the reference's op sequence
-on torch.
+on torch, and so does learn() with more atoms than the loss kernel takes (``_C.DIST_MAX_N``).
 """
 from typing import Any, Optional
 
@@ -42,6 +42,9 @@ class C51Policy(DistDQNMixin, DQNPolicy):
 
     def _q_weights(self) -> Optional[torch.Tensor]:
         return self.support
+
+    def _num_columns(self) -> int:
+        return self._num_atoms
 
     def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
         """c51.py:65-66: the support per row; the n-step kernel turns it into

@@ -20,9 +20,11 @@ train-mode action is ``gumbel_sample`` (policy/pg.py: the same distribution in o
 place of ``dist.sample()``; ``batch.weight`` leaves as an f32 device tensor.  ``fused = False``
 is the reference's op sequence, the comparison leg and the CPU path.
 
-What stays on torch is what stays there for SACPolicy.  Not built: action masks, and a conv
-trunk shared between the actor and the critics under graph replay (each network here owns its
-parameters).
+What stays on torch is what stays there for SACPolicy.  Not built: ``obs.mask`` support, and a
+conv trunk shared between the actor and the critics under graph replay (each network here owns
+its parameters).  An actor that masks illegal actions itself, with -inf logits, is safe on
+either path: the kernels give such an entry probability 0 and gradient exactly 0, as torch's
+Categorical does (tests/test_gpu_offpolicy_edges.py).
 """
 from typing import Any, Optional, Tuple, Union
 

@@ -147,12 +147,17 @@ class DQNPolicy(BasePolicy):
         p = next(self.model.parameters(), None)
         return p is not None and p.is_cuda
 
+    def _fused_learn(self) -> bool:
+        """learn() runs the fused loss and the flat optimiser pass; False: the torch
+        formulation (``_learn_torch``), as with ``fused = False``."""
+        return self.fused and self._on_device()
+
     def _flat_adam(self) -> Optional[FlatAdam]:
         """The flat gradient / optimiser storage of the Q-network when the optimiser is a plain
         Adam or RMSprop over exactly its parameters (None otherwise: torch's step runs).  The
         target network's parameters then become views into a second flat buffer laid out as
         the first (flat_learn.mirror_target)."""
-        if not (self.fused and self.fused_adam and self._on_device()):
+        if not (self.fused_adam and self._fused_learn()):
             return None
         fa = self._flat
         if fa is None:
@@ -284,7 +289,7 @@ class DQNPolicy(BasePolicy):
         weight = batch.pop("weight", None)
         obs = batch.obs
         net_in = obs.obs if isinstance(obs, Batch) and "obs" in obs else obs
-        if not (self.fused and self._on_device()):
+        if not self._fused_learn():
             loss, td = self._learn_torch(batch, weight)
         else:
             dev = next(self.model.parameters()).device

@@ -148,6 +148,15 @@ class DistDQNMixin:
         """The [N] weights that reduce the atoms to a Q-value; None: their mean."""
         raise NotImplementedError
 
+    def _num_columns(self) -> int:
+        """N: the atoms or quantiles per action."""
+        raise NotImplementedError
+
+    def _fused_learn(self) -> bool:
+        """More columns than the loss kernels stage (_C.DIST_MAX_N, their argument error):
+        learn() takes the torch formulation.  tsrl_dist_select has no such limit."""
+        return super()._fused_learn() and self._num_columns() <= _C.DIST_MAX_N
+
     def _greedy_act(self, logits: torch.Tensor) -> torch.Tensor:
         if self.fused and logits.is_cuda and logits.dim() == 3:
             return dist_select(logits, None, self._q_weights())[1]

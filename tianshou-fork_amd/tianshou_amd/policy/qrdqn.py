@@ -6,7 +6,8 @@ The network returns N quantile values per action, [b, A, N] (utils/net.py
 tsrl_dist_select (the mean over the quantiles, the greedy action, its row); learn() is
 tsrl_qr_loss_fwd_bwd, which walks the N x N quantile pairs of a row out of LDS instead of
 building the reference's [b, N, N] tensors.  ``fused = False`` runs the reference's op sequence
-on torch.
+on torch, and so does learn() with more quantiles than the loss kernel takes
+(``_C.DIST_MAX_N``).
 """
 import warnings
 from typing import Any, Optional
@@ -40,6 +41,9 @@ class QRDQNPolicy(DistDQNMixin, DQNPolicy):
 
     def _q_weights(self) -> Optional[torch.Tensor]:
         return None
+
+    def _num_columns(self) -> int:
+        return self._num_quantiles
 
     def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
         """qrdqn.py:58-68: the target network's quantiles of the online network's greedy
