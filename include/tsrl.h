@@ -901,6 +901,56 @@ int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* ret
                          double* partials, float* loss, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * IQNPolicy / ImplicitQuantileNetwork (tianshou/policy/modelfree/iqn.py, utils/net/
+ * discrete.py:124-214), csrc/dqn_dist.hip.  The network's head output is quantile-major, [b, n,
+ * num_actions] seen as a [b, num_actions, n] view: tsrl_iqn_select and tsrl_iqn_loss_fwd_bwd
+ * take the element strides of the action and quantile axes and accept exactly the two layouts
+ * (n, 1) (contiguous [b, A, n]) and (1, A) (that view); a batch row is A * n elements.  Anything
+ * else is an argument error.
+ * tsrl_iqn_embed_fwd: the cosine embedding and its Hadamard product with the state embedding
+ *   (discrete.py:143-155, 211-212).  h [b, d], taus [b, n], w [d, c], bias [d];
+ *   e[(r,n)][d] = relu(bias[d] + sum_k cos(arg_k) w[d][k]) and out[(r,n)][d] = h[r][d] *
+ *   e[(r,n)][d], both [b * n, d].  arg_k = fl32(fl32(fl32(pi) * (k + 1)) * taus[r][n]), the f32
+ *   argument torch forms; the cosine and the k-sum are f64 (FMA in index order from the bias);
+ *   e and out are each rounded once from f64.  relu keeps a NaN.  1 <= c <=
+ *   TSRL_IQN_MAX_COSINES (the cosines of a fraction are staged in LDS).  b == 0 launches
+ *   nothing.
+ * tsrl_iqn_embed_bwd: g_h[r][d] = sum_n g_out[(r,n)][d] e[(r,n)][d] (f64, n in index order,
+ *   rounded once); g_z[(r,n)][d] = e > 0 ? g_out * h[r][d] : 0 (torch's ReLU backward: zero at
+ *   z == 0, a NaN e passes the gradient); cos_out (may be NULL; needs taus) receives the cosine
+ *   features [b * n, c] in f32, the other operand of the weight gradient g_z^T cos.  g_b [d]
+ *   (may be NULL; needs the workspace gb_part, b * d doubles) receives the bias gradient sum
+ *   g_z: per row an f64 sum over n, then the rows in row order by a second launch, rounded
+ *   once.  When b == 0 nothing is launched or written.  taus get no gradient.
+ * tsrl_iqn_select: tsrl_dist_select for sel [b, A, n] and eval [b, A, m] (may be NULL), each
+ *   with its own strides: q_out[r][a] = mean_k sel[r][a][k] (an f64 sum rounded once), act_out
+ *   the first argmax by torch's rule, row_out[r][:] = eval[r][act[r]][:] ([b, m]) or, with eval
+ *   NULL, sel's row ([b, n]).  Each output may be NULL; b == 0 launches nothing.
+ * tsrl_iqn_loss_fwd_bwd: learn() (iqn.py:93-108).  curr [b, A, n] and grad with strides (sa, sn),
+ *   returns [b, m], taus [b, n], weight [b] or NULL.  With u_ij = returns[r][j] -
+ *   curr[r][act[r]][i] and k_ij = |taus[r][i] - 1{u_ij <= 0}|: huber_r = (1/n) sum_i sum_j
+ *   smooth_l1(u_ij) k_ij, prio[r] = (1/n) sum_ij smooth_l1(u_ij), *loss = mean(huber * weight),
+ *   grad[r][act[r]][i] = -(weight[r] / (b n)) sum_j clamp(u_ij, -1, 1) k_ij, zero elsewhere.
+ *   2 <= n, m <= TSRL_DIST_MAX_N.  Edges, summation order and partials as
+ *   tsrl_qr_loss_fwd_bwd; with m == n and every taus row equal to tau_hat the outputs are that
+ *   function's bit for bit.
+ * ------------------------------------------------------------------------------- */
+#define TSRL_IQN_MAX_COSINES 256
+int tsrl_iqn_embed_fwd(const float* h, const float* taus, const float* w, const float* bias,
+                       int64_t b, int64_t n, int64_t d, int64_t c, float* e, float* out,
+                       void* stream);
+int tsrl_iqn_embed_bwd(const float* g_out, const float* e, const float* h, const float* taus,
+                       int64_t b, int64_t n, int64_t d, int64_t c, float* g_h, float* g_z,
+                       float* cos_out, double* gb_part, float* g_b, void* stream);
+int tsrl_iqn_select(const float* sel, int64_t sel_sa, int64_t sel_sn, const float* eval,
+                    int64_t eval_sa, int64_t eval_sm, int64_t b, int64_t num_actions, int64_t n,
+                    int64_t m, float* q_out, int64_t* act_out, float* row_out, void* stream);
+int tsrl_iqn_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn, const int64_t* act,
+                          const float* returns, const float* taus, const float* weight,
+                          int64_t b, int64_t num_actions, int64_t n, int64_t m, float* grad,
+                          float* prio, double* partials, float* loss, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * RainbowPolicy (tianshou/policy/modelfree/rainbow.py): NoisyLinear (utils/net/discrete.py:
  * 319-394) and the dueling combine (utils/net/common.py:276-284), csrc/noisy.hip.  All tensors
  * f32 and 4-byte aligned unless noted; no call synchronises or allocates, so each can be

@@ -5,7 +5,10 @@
 //   c51_loss:     the categorical projection, the cross-entropy and its gradient
 //                 (c51.py:82-102) without the [b, N, N] projection tensor;
 //   qr_loss:      the pairwise quantile Huber loss, the priorities and the gradient
-//                 (qrdqn.py:82-93) without its [b, N, N] tensors.
+//                 (qrdqn.py:82-93) without its [b, N, N] tensors;
+//   iqn_*:        IQNPolicy's siblings of dist_select and qr_loss for N online against M target
+//                 quantiles at per-row fractions, read through strides, and the cosine
+//                 embedding of ImplicitQuantileNetwork with its backward (further down).
 // One workgroup per batch row, lanes over the N atoms (a loop when N exceeds the workgroup):
 // b is 32 to a few hundred, so the grid is b workgroups of one to four waves and the cost is
 // launch latency.  Sums are f64 in a fixed order (lanes by xor butterfly, waves in wave order,
@@ -249,6 +252,233 @@ inline unsigned atom_threads(int64_t N) {
     return (unsigned)(t < TPB ? t : TPB);
 }
 
+// -- IQNPolicy (tianshou/policy/modelfree/iqn.py, utils/net/discrete.py:124-214) ------------------
+// The network's head output is quantile-major, [b, N, A] seen as a [b, A, N] view: the select
+// and loss kernels take the element strides of the A and N axes (sA, sN) and read either layout
+// in place; a batch row is always A * N elements long.
+constexpr int kMaxCos = TSRL_IQN_MAX_COSINES;  // cosines staged per fraction
+constexpr int kFrac = 8;                       // fractions per workgroup: 8 * 256 doubles of LDS
+
+// cos(pi (k + 1) tau) with the argument formed in f32 as CosineEmbeddingNetwork.forward forms
+// it (an f32 arange times pi rounded to f32, then times tau); the cosine itself in f64.
+__device__ __forceinline__ double iqn_cos(int k, float tau) {
+    const float ipi = (float)(k + 1) * 3.14159274101257324f;
+    const float arg = tau * ipi;
+    return cos((double)arg);
+}
+
+// Workgroup (x, y): row x / nch, fractions (x % nch) * kFrac ..., features y * TPB ...  The
+// fractions' cosines are staged once in LDS (f64); a thread owns feature d and walks W[d][:]
+// once for its kFrac accumulators.  The k-sum is f64 FMA in index order starting from the bias;
+// e and out are each rounded once from f64.
+__global__ __launch_bounds__(TPB) void iqn_embed_fwd_kernel(
+    const float* __restrict__ h, const float* __restrict__ taus, const float* __restrict__ W,
+    const float* __restrict__ bias, int64_t N, int64_t D, int C, int64_t nch,
+    float* __restrict__ e, float* __restrict__ out) {
+    __shared__ double s_cos[kFrac][kMaxCos];
+    const int t = threadIdx.x;
+    const int64_t r = blockIdx.x / nch, n0 = (blockIdx.x % nch) * kFrac;
+    const int nf = (int)(N - n0 < kFrac ? N - n0 : kFrac);
+    for (int f = t; f < kFrac * C; f += TPB) {
+        const int j = f / C, k = f - j * C;
+        s_cos[j][k] = j < nf ? iqn_cos(k, taus[r * N + n0 + j]) : 0.0;
+    }
+    __syncthreads();
+    const int64_t d = (int64_t)blockIdx.y * TPB + t;
+    if (d >= D) return;
+    double acc[kFrac];
+    const double bd = (double)bias[d];
+#pragma unroll
+    for (int j = 0; j < kFrac; ++j) acc[j] = bd;
+    const float* w = W + d * C;
+    for (int k = 0; k < C; ++k) {
+        const double wk = (double)w[k];
+#pragma unroll
+        for (int j = 0; j < kFrac; ++j) acc[j] = fma(s_cos[j][k], wk, acc[j]);
+    }
+    const double hd = (double)h[r * D + d];
+#pragma unroll
+    for (int j = 0; j < kFrac; ++j) {
+        if (j < nf) {
+            const double z = acc[j];
+            const double ez = z > 0.0 ? z : (z != z ? z : 0.0);  // torch's relu keeps a NaN
+            const int64_t o = (r * N + n0 + j) * D + d;
+            e[o] = (float)ez;
+            out[o] = (float)(hd * ez);
+        }
+    }
+}
+
+// Workgroup (x, y): row x, features y * TPB ...; a thread owns (row, d) and walks the N
+// fractions in index order (g_h: an f64 sum rounded once).  The y == 0 workgroups also write
+// the row's cosine features when asked.  gb_part (optional) gets the row's share of the bias
+// gradient, sum_n g_z[(r,n)][d] in f64; iqn_gb_fold_kernel sums the rows in row order.
+__global__ __launch_bounds__(TPB) void iqn_embed_bwd_kernel(
+    const float* __restrict__ g_out, const float* __restrict__ e, const float* __restrict__ h,
+    const float* __restrict__ taus, int64_t N, int64_t D, int C, float* __restrict__ g_h,
+    float* __restrict__ g_z, float* __restrict__ cos_out, double* __restrict__ gb_part) {
+    const int t = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    if (cos_out && blockIdx.y == 0) {
+        const int64_t nel = N * C;
+        for (int64_t f = t; f < nel; f += TPB) {
+            const int64_t n = f / C;
+            cos_out[r * nel + f] = (float)iqn_cos((int)(f - n * C), taus[r * N + n]);
+        }
+    }
+    const int64_t d = (int64_t)blockIdx.y * TPB + t;
+    if (d >= D) return;
+    const float hd = h[r * D + d];
+    double s = 0.0, sb = 0.0;
+    for (int64_t n = 0; n < N; ++n) {
+        const int64_t o = (r * N + n) * D + d;
+        const float g = g_out[o], ev = e[o];
+        s += (double)g * (double)ev;
+        const bool dead = ev <= 0.0f;  // torch's threshold_backward: zero at z == 0
+        g_z[o] = dead ? 0.0f : g * hd;
+        sb += dead ? 0.0 : (double)g * (double)hd;
+    }
+    g_h[r * D + d] = (float)s;
+    if (gb_part) gb_part[r * D + d] = sb;
+}
+
+// g_b[d] = sum_r gb_part[r][d], rows in row order, rounded once.
+__global__ __launch_bounds__(TPB) void iqn_gb_fold_kernel(const double* __restrict__ gb_part,
+                                                          int64_t B, int64_t D,
+                                                          float* __restrict__ g_b) {
+    const int64_t d = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (d >= D) return;
+    double s = 0.0;
+    for (int64_t r = 0; r < B; ++r) s += gb_part[r * D + d];
+    g_b[d] = (float)s;
+}
+
+// dist_select_kernel with strides, a mean only, and an eval of its own column count M.
+__global__ __launch_bounds__(TPB) void iqn_select_kernel(
+    const float* __restrict__ sel, int64_t sA, int64_t sN, const float* __restrict__ eval,
+    int64_t eA, int64_t eM, int64_t A, int64_t N, int64_t M, float* __restrict__ q_out,
+    int64_t* __restrict__ act_out, float* __restrict__ row_out) {
+    __shared__ float s_best[NW];
+    __shared__ int64_t s_arg[NW];
+    __shared__ int64_t s_act;
+    const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+    const int64_t r = blockIdx.x;
+    const float* row = sel + r * A * N;
+    const double inv_n = 1.0 / (double)N;
+    float best = 0.0f;
+    int64_t arg = -1;
+    for (int64_t a = wv; a < A; a += NW) {
+        const float* x = row + a * sA;
+        double acc = 0.0;
+        for (int64_t n = lane; n < N; n += kWave) acc += (double)x[n * sN];
+        acc = wave_sum(acc);
+        const float q = (float)(acc * inv_n);
+        if (q_out && lane == 0) q_out[r * A + a] = q;
+        if (arg < 0 || beats_at(q, a, best, arg)) {
+            best = q;
+            arg = a;
+        }
+    }
+    if (lane == 0) {
+        s_best[wv] = best;
+        s_arg[wv] = arg;
+    }
+    __syncthreads();
+    if (t == 0) {
+        best = s_best[0];
+        arg = s_arg[0];  // wave 0 always holds action 0
+        for (int i = 1; i < NW; ++i)
+            if (s_arg[i] >= 0 && beats_at(s_best[i], s_arg[i], best, arg)) {
+                best = s_best[i];
+                arg = s_arg[i];
+            }
+        s_act = arg;
+        if (act_out) act_out[r] = arg;
+    }
+    if (!row_out) return;
+    __syncthreads();
+    if (eval) {
+        const float* src = eval + r * A * M + s_act * eA;
+        for (int64_t n = t; n < M; n += TPB) row_out[r * M + n] = src[n * eM];
+    } else {
+        const float* src = row + s_act * sA;
+        for (int64_t n = t; n < N; n += TPB) row_out[r * N + n] = src[n * sN];
+    }
+}
+
+// iqn.py:93-108 for one row: qr_loss_kernel's pair walk with the row's own fractions and M
+// targets (LDS: the M returns).  A thread owns the current quantile i; with M == N and
+// taus[r] == tau_hat every operation is qr_loss_kernel's, in its order.
+__global__ __launch_bounds__(TPB) void iqn_loss_kernel(
+    const float* __restrict__ curr, int64_t sA, int64_t sN, const int64_t* __restrict__ act,
+    const float* __restrict__ returns, const float* __restrict__ taus,
+    const float* __restrict__ weight, int64_t b, int64_t A, int64_t N, int64_t M,
+    float* __restrict__ grad, float* __restrict__ prio, double* __restrict__ partials,
+    float* __restrict__ loss) {
+    extern __shared__ float lds[];
+    __shared__ double red[NW];
+    const int t = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    const int64_t a64 = act[r];
+    const int64_t a = (a64 >= 0 && a64 < A) ? a64 : -1;
+    float* g_row = grad + r * A * N;
+    for (int64_t f = t; f < A * N; f += blockDim.x) {
+        const int64_t fa = f / N;
+        if (fa != a) g_row[fa * sA + (f - fa * N) * sN] = 0.0f;
+    }
+    if (a < 0) {
+        if (t == 0) {
+            prio[r] = NAN;
+            put_term((double)NAN, partials, loss);
+        }
+        return;
+    }
+    for (int64_t j = t; j < M; j += blockDim.x) lds[j] = returns[r * M + j];
+    __syncthreads();
+    const double wr = weight ? (double)weight[r] : 1.0;
+    const double inv_n = 1.0 / (double)N;
+    const double gscale = wr / ((double)b * (double)N);
+    const float* c_row = curr + r * A * N + a * sA;
+    const float* tau_row = taus + r * N;
+    double hub = 0.0, pri = 0.0;
+    for (int64_t i = t; i < N; i += blockDim.x) {
+        const double th = (double)c_row[i * sN], tau = (double)tau_row[i];
+        const double k_neg = fabs(tau - 1.0), k_pos = fabs(tau);  // |tau - 1{u <= 0}|
+        double hi = 0.0, g = 0.0;
+        for (int64_t j = 0; j < M; ++j) {
+            const double u = (double)lds[j] - th;
+            const double au = fabs(u);
+            const double h = au < 1.0 ? 0.5 * u * u : au - 0.5;  // smooth_l1, beta 1
+            const double k = u <= 0.0 ? k_neg : k_pos;
+            hi += h * k;
+            pri += h;
+            g += fmin(fmax(u, -1.0), 1.0) * k;
+        }
+        if (hi != hi) {
+            // as qr_loss_kernel: a NaN u_ij keeps its NaN in the derivative; inf * 0 (a
+            // fraction of exactly 0) takes the second pass and gets the first one's result
+            g = 0.0;
+            for (int64_t j = 0; j < M; ++j) {
+                const double u = (double)lds[j] - th;
+                g += (u != u ? u : fmin(fmax(u, -1.0), 1.0)) * (u <= 0.0 ? k_neg : k_pos);
+            }
+        }
+        hub += hi;
+        g_row[a * sA + i * sN] = (float)(-g * gscale);
+    }
+    const double hs = block_sum(hub, red) * inv_n;
+    const double ps = block_sum(pri, red) * inv_n;
+    if (t == 0) {
+        prio[r] = (float)ps;
+        put_term(hs * wr, partials, loss);
+    }
+}
+
+// Either layout of a [b, A, N] view whose batch rows are A * N elements long.
+inline bool row_strides_ok(int64_t sa, int64_t sn, int64_t A, int64_t N) {
+    return (sa == N && sn == 1) || (sa == 1 && sn == A);
+}
+
 }  // namespace
 }  // namespace tsrl
 
@@ -310,6 +540,93 @@ extern "C" int tsrl_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const
         hipLaunchKernelGGL(dist_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
                            partials, b, loss);
         TSRL_LAUNCH_CHECK("tsrl_qr_loss_fwd_bwd (fold)");
+    }
+    return 0;
+}
+
+extern "C" int tsrl_iqn_embed_fwd(const float* h, const float* taus, const float* w,
+                                  const float* bias, int64_t b, int64_t n, int64_t d, int64_t c,
+                                  float* e, float* out, void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && n >= 1 && d >= 1 && c >= 1 && c <= kMaxCos,
+                   "tsrl_iqn_embed_fwd: need b >= 0, n >= 1, d >= 1 and 1 <= c <= %d", kMaxCos);
+    const int64_t nch = (n + kFrac - 1) / kFrac, ny = (d + TPB - 1) / TPB;
+    TSRL_CHECK_ARG(b * nch < ((int64_t)1 << 31) && ny <= 65535,
+                   "tsrl_iqn_embed_fwd: need b * ceil(n / %d) < 2^31 and d <= %d", kFrac,
+                   65535 * TPB);
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(h && taus && w && bias && e && out, "tsrl_iqn_embed_fwd: null pointer");
+    hipLaunchKernelGGL(iqn_embed_fwd_kernel, dim3((unsigned)(b * nch), (unsigned)ny), dim3(TPB),
+                       0, as_stream(stream), h, taus, w, bias, n, d, (int)c, nch, e, out);
+    TSRL_LAUNCH_CHECK("tsrl_iqn_embed_fwd");
+    return 0;
+}
+
+extern "C" int tsrl_iqn_embed_bwd(const float* g_out, const float* e, const float* h,
+                                  const float* taus, int64_t b, int64_t n, int64_t d, int64_t c,
+                                  float* g_h, float* g_z, float* cos_out, double* gb_part,
+                                  float* g_b, void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && b < ((int64_t)1 << 31) && n >= 1 && d >= 1 && c >= 1 &&
+                       (d + TPB - 1) / TPB <= 65535,
+                   "tsrl_iqn_embed_bwd: need 0 <= b < 2^31, n >= 1, 1 <= d <= %d and c >= 1",
+                   65535 * TPB);
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(g_out && e && h && g_h && g_z && (!cos_out || taus) && (!g_b == !gb_part),
+                   "tsrl_iqn_embed_bwd: null pointer (cos_out needs taus, g_b needs gb_part)");
+    hipLaunchKernelGGL(iqn_embed_bwd_kernel, dim3((unsigned)b, (unsigned)((d + TPB - 1) / TPB)),
+                       dim3(TPB), 0, as_stream(stream), g_out, e, h, taus, n, d, (int)c, g_h,
+                       g_z, cos_out, gb_part);
+    TSRL_LAUNCH_CHECK("tsrl_iqn_embed_bwd");
+    if (g_b) {
+        hipLaunchKernelGGL(iqn_gb_fold_kernel, dim3((unsigned)((d + TPB - 1) / TPB)), dim3(TPB), 0,
+                           as_stream(stream), gb_part, b, d, g_b);
+        TSRL_LAUNCH_CHECK("tsrl_iqn_embed_bwd (bias fold)");
+    }
+    return 0;
+}
+
+extern "C" int tsrl_iqn_select(const float* sel, int64_t sel_sa, int64_t sel_sn,
+                               const float* eval, int64_t eval_sa, int64_t eval_sm, int64_t b,
+                               int64_t num_actions, int64_t n, int64_t m, float* q_out,
+                               int64_t* act_out, float* row_out, void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 1,
+                   "tsrl_iqn_select: need 0 <= b < 2^31, num_actions >= 1 and n >= 1");
+    TSRL_CHECK_ARG(row_strides_ok(sel_sa, sel_sn, num_actions, n),
+                   "tsrl_iqn_select: sel strides (%lld, %lld) are neither [b, A, N] nor the "
+                   "[b, N, A] view", (long long)sel_sa, (long long)sel_sn);
+    TSRL_CHECK_ARG(!eval || (m >= 1 && row_strides_ok(eval_sa, eval_sm, num_actions, m)),
+                   "tsrl_iqn_select: eval needs m >= 1 and strides of [b, A, M] or its "
+                   "[b, M, A] view");
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(sel, "tsrl_iqn_select: null pointer");
+    hipLaunchKernelGGL(iqn_select_kernel, dim3((unsigned)b), dim3(TPB), 0, as_stream(stream), sel,
+                       sel_sa, sel_sn, eval, eval_sa, eval_sm, num_actions, n, m, q_out, act_out,
+                       row_out);
+    TSRL_LAUNCH_CHECK("tsrl_iqn_select");
+    return 0;
+}
+
+extern "C" int tsrl_iqn_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn,
+                                     const int64_t* act, const float* returns, const float* taus,
+                                     const float* weight, int64_t b, int64_t num_actions,
+                                     int64_t n, int64_t m, float* grad, float* prio,
+                                     double* partials, float* loss, void* stream) {
+    TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 2 && n <= kMaxN &&
+                       m >= 2 && m <= kMaxN,
+                   "tsrl_iqn_loss_fwd_bwd: need 1 <= b < 2^31, num_actions >= 1, 2 <= n, m <= %d",
+                   (int)kMaxN);
+    TSRL_CHECK_ARG(row_strides_ok(sa, sn, num_actions, n),
+                   "tsrl_iqn_loss_fwd_bwd: strides (%lld, %lld) are neither [b, A, N] nor the "
+                   "[b, N, A] view", (long long)sa, (long long)sn);
+    TSRL_CHECK_ARG(curr && act && returns && taus && grad && prio && loss && (b == 1 || partials),
+                   "tsrl_iqn_loss_fwd_bwd: null pointer");
+    hipLaunchKernelGGL(iqn_loss_kernel, dim3((unsigned)b), dim3(atom_threads(n)),
+                       (size_t)m * sizeof(float), as_stream(stream), curr, sa, sn, act, returns,
+                       taus, weight, b, num_actions, n, m, grad, prio, partials, loss);
+    TSRL_LAUNCH_CHECK("tsrl_iqn_loss_fwd_bwd");
+    if (b > 1) {
+        hipLaunchKernelGGL(dist_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
+                           partials, b, loss);
+        TSRL_LAUNCH_CHECK("tsrl_iqn_loss_fwd_bwd (fold)");
     }
     return 0;
 }

@@ -235,6 +235,13 @@ _SIGS = {
                                _p, _p], ctypes.c_int),
     "tsrl_qr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
                              ctypes.c_int),
+    "tsrl_iqn_embed_fwd": ([_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_iqn_embed_bwd": ([_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
+                           ctypes.c_int),
+    "tsrl_iqn_select": ([_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p,
+                         _p], ctypes.c_int),
+    "tsrl_iqn_loss_fwd_bwd": ([_p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p,
+                               _p, _p, _p], ctypes.c_int),
     "tsrl_noisy_eps": ([_p, _i64, _p, _p], ctypes.c_int),
     "tsrl_noisy_weights": ([_p, _i64, _i64, _p], ctypes.c_int),
     "tsrl_noisy_grads": ([_p, _p, _p, _p, _i64, _i64, _p, _p, _p], ctypes.c_int),
@@ -269,6 +276,7 @@ NOISY_DESC_WORDS = 10
 DUELING_MAX_ROW = 4096        # TSRL_DUELING_MAX_ROW
 ERR_DUELING_ROW = 100001      # TSRL_ERR_DUELING_ROW
 DIST_MAX_N = 4096             # TSRL_DIST_MAX_N: atoms / quantiles the C51 and QR loss kernels take
+IQN_MAX_COSINES = 256         # TSRL_IQN_MAX_COSINES: cosines tsrl_iqn_embed_fwd stages per fraction
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

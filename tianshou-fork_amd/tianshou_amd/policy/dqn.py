@@ -19,8 +19,9 @@ the comparison leg of tools/dqn_update_bench.py.
 
 The distributional subclasses C51Policy (policy/c51.py) and QRDQNPolicy (policy/qrdqn.py) fill
 the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_weight``,
-``_before_forward``, ``_fused_loss``) and reuse the flat storage, the sync and the graph replay
-as they are; RainbowPolicy (policy/rainbow.py) is C51Policy over NoisyLinear layers.
+``_before_forward``, ``_forward_q``, ``_fused_loss``) and reuse the flat storage, the sync and
+the graph replay as they are; RainbowPolicy (policy/rainbow.py) is C51Policy over NoisyLinear
+layers and IQNPolicy (policy/iqn.py) QRDQNPolicy over ImplicitQuantileNetwork.
 """
 from copy import deepcopy
 from typing import Any, Dict, Optional, Union
@@ -348,6 +349,11 @@ class DQNPolicy(BasePolicy):
         ``_fused_loss``."""
         return None
 
+    def _forward_q(self, obs, info, aux):
+        """The online network's output at obs and what ``_fused_loss`` gets as ``aux``
+        (IQNPolicy hands fractions in and takes them back)."""
+        return self.model(obs, state=None, info=info)[0], aux
+
     def _fused_loss(self, q, act, returns, weight, aux, td_out, loss_out):
         """(loss, per-row vector that leaves as batch.weight) of the network output q."""
         return _DQNLoss.apply(q, (act, returns, weight, self._clip_loss_grad, td_out, loss_out))
@@ -356,7 +362,7 @@ class DQNPolicy(BasePolicy):
               td_out=None, loss_out=None):
         """Forward, fused TD loss, backward, optimiser step; returns (loss, td_error)."""
         aux = self._before_forward(info, *extra)
-        q, _ = self.model(obs, state=None, info=info)
+        q, aux = self._forward_q(obs, info, aux)
         loss, td = self._fused_loss(q, act, returns, weight, aux, td_out, loss_out)
         if fa is None:
             self.optim.zero_grad()

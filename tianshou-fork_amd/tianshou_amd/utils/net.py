@@ -2,7 +2,8 @@
 tianshou 0.5.1 checkpoints (utils/net/common.py:56-285, continuous.py:87-235,
 discrete.py:12-121, 319-394).  The GEMMs run through PyTorch-ROCm (hipBLASLt) on the GPU;
 NoisyLinear's effective parameters, its sigma gradients and the dueling combine are the kernels
-of csrc/noisy.hip."""
+of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd
+(csrc/dqn_dist.hip)."""
 import contextlib
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
 
@@ -659,6 +660,126 @@ class DiscreteCritic(nn.Module):
     def forward(self, obs, **kwargs: Any):
         logits, _ = self.preprocess(obs, state=kwargs.get("state", None))
         return self.last(logits)
+
+
+class _IQNEmbedFn(torch.autograd.Function):
+    """out [b * N, D] = h[r] * relu(cosines(taus) W^T + bias): the cosine embedding and its
+    Hadamard product with the state embedding as tsrl_iqn_embed_fwd / tsrl_iqn_embed_bwd.  The
+    weight gradient is _linear_grads' (g_z, cosine features); the bias gradient comes out of the
+    backward kernel's own f64 fold (at one-feature shapes an f32 row sum of g_z deviated from
+    f64 by 20 x what torch's own sum did); taus get none."""
+
+    @staticmethod
+    def forward(ctx, h, taus, weight, bias):
+        hc, tc = h.detach().float().contiguous(), taus.detach().float().contiguous()
+        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
+        (b, D), N, C = hc.shape, tc.shape[1], wc.shape[1]
+        if tc.dim() != 2 or tc.shape[0] != b or wc.shape != (D, C) or bc.shape != (D,):
+            raise ValueError(f"_IQNEmbedFn: h {tuple(hc.shape)}, taus {tuple(tc.shape)}, weight "
+                             f"{tuple(wc.shape)}, bias {tuple(bc.shape)} do not fit")
+        e = torch.empty(b * N, D, dtype=torch.float32, device=hc.device)
+        out = torch.empty_like(e)
+        _C.check(_C.lib().tsrl_iqn_embed_fwd(
+            _C.ptr(hc), _C.ptr(tc), _C.ptr(wc, torch.float32), _C.ptr(bc, torch.float32), b, N,
+            D, C, _C.ptr(e), _C.ptr(out), _C.stream_ptr(hc.device)), "tsrl_iqn_embed_fwd")
+        ctx.save_for_backward(h, tc, e, weight, bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        h, taus, e, weight, bias = ctx.saved_tensors
+        need_h, _, need_w, need_b = ctx.needs_input_grad
+        (b, D), N, C = h.shape, taus.shape[1], weight.shape[1]
+        if torch.is_grad_enabled():
+            # a create_graph pass: the reference's op sequence from the inputs again, so the
+            # double backward sees the whole graph
+            emb = torch.relu(torch.addmm(bias, CosineEmbeddingNetwork.cosines(taus, C),
+                                         weight.t())).view(b, N, D)
+            out = (h.unsqueeze(1) * emb).view(b * N, D)
+            ins = [t for t, need in ((h, need_h), (weight, need_w), (bias, need_b)) if need]
+            grads = iter(torch.autograd.grad(out, ins, g_out, create_graph=True))
+            return (next(grads) if need_h else None, None, next(grads) if need_w else None,
+                    next(grads) if need_b else None)
+        h_dtype, h = h.dtype, h.detach().float().contiguous()
+        g = g_out.float().contiguous()
+        g_h = torch.empty_like(h)
+        g_z = torch.empty_like(e)
+        cos = torch.empty(b * N, C, dtype=torch.float32, device=h.device) if need_w else None
+        gb = torch.empty(D, dtype=torch.float32, device=h.device) if need_b else None
+        part = torch.empty(b, D, dtype=torch.float64, device=h.device) if need_b else None
+        _C.check(_C.lib().tsrl_iqn_embed_bwd(
+            _C.ptr(g), _C.ptr(e), _C.ptr(h), _C.ptr(taus), b, N, D, C, _C.ptr(g_h), _C.ptr(g_z),
+            _C.ptr(cos), _C.ptr(part), _C.ptr(gb), _C.stream_ptr(h.device)),
+            "tsrl_iqn_embed_bwd")
+        _, gw, _ = _linear_grads(cos, weight, g_z, False, need_w, False)
+        return g_h.to(h_dtype) if need_h else None, None, gw, gb
+
+
+class CosineEmbeddingNetwork(nn.Module):
+    """IQN's cosine embedding (utils/net/discrete.py:124-155): a fraction in [0, 1] becomes
+    relu(Linear(cos(pi i tau), i = 1..num_cosines)).  Module layout (``net.0``) as the
+    reference's."""
+
+    def __init__(self, num_cosines: int, embedding_dim: int) -> None:
+        super().__init__()
+        self.net = nn.Sequential(nn.Linear(num_cosines, embedding_dim), nn.ReLU())
+        self.num_cosines = num_cosines
+        self.embedding_dim = embedding_dim
+
+    @staticmethod
+    def cosines(taus: torch.Tensor, num_cosines: int) -> torch.Tensor:
+        """discrete.py:147-152: cos(i pi tau), [b * N, num_cosines]."""
+        batch_size, N = taus.shape[0], taus.shape[1]
+        i_pi = np.pi * torch.arange(start=1, end=num_cosines + 1, dtype=taus.dtype,
+                                    device=taus.device).view(1, 1, num_cosines)
+        return torch.cos(taus.view(batch_size, N, 1) * i_pi).view(batch_size * N, num_cosines)
+
+    def forward(self, taus: torch.Tensor) -> torch.Tensor:
+        cosines = self.cosines(taus, self.num_cosines)
+        return self.net(cosines).view(taus.shape[0], taus.shape[1], self.embedding_dim)
+
+    def hadamard(self, h: torch.Tensor, taus: torch.Tensor, fused: bool = True) -> torch.Tensor:
+        """(h.unsqueeze(1) * self(taus)).view(b * N, -1) (discrete.py:211-212): one launch each
+        way on the GPU; the reference's torch lines on the CPU, with ``fused`` False and with
+        more cosines than the kernel stages (_C.IQN_MAX_COSINES)."""
+        lin = self.net[0]
+        if fused and h.is_cuda and taus.is_cuda and h.dim() == 2 and \
+                h.dtype == torch.float32 and taus.dtype == torch.float32 and \
+                lin.weight.dtype == torch.float32 and self.num_cosines <= _C.IQN_MAX_COSINES:
+            return _IQNEmbedFn.apply(h, taus, lin.weight, lin.bias)
+        return (h.unsqueeze(1) * self(taus)).view(taus.shape[0] * taus.shape[1], -1)
+
+
+class ImplicitQuantileNetwork(DiscreteCritic):
+    """IQN's quantile Q-network (utils/net/discrete.py:158-214): constructor arguments,
+    attributes and state_dict keys (``preprocess.*``, ``last.*``, ``embed_model.net.0.*``) as
+    the reference's.  ``forward`` returns ((out, taus), hidden) with out the [b, A, N] view of
+    the head's [b, N, A] output.  ``taus`` None draws them where the reference does (after the
+    preprocess forward, one torch.rand), so a seeded CPU run consumes the reference's stream;
+    IQNPolicy hands recorded or pre-drawn fractions in.  ``fused_embed = False``: the torch
+    lines (``IQNPolicy.fused`` sets it on its networks)."""
+
+    fused_embed = True
+
+    def __init__(self, preprocess_net: nn.Module, action_shape, hidden_sizes: Sequence[int] = (),
+                 num_cosines: int = 64, preprocess_net_output_dim: Optional[int] = None,
+                 device="cpu") -> None:
+        last_size = int(np.prod(action_shape))
+        super().__init__(preprocess_net, hidden_sizes, last_size, preprocess_net_output_dim,
+                         device)
+        self.input_dim = getattr(preprocess_net, "output_dim", preprocess_net_output_dim)
+        self.embed_model = CosineEmbeddingNetwork(num_cosines, self.input_dim).to(device)
+
+    def forward(self, obs, sample_size: int, taus: Optional[torch.Tensor] = None,
+                **kwargs: Any):
+        logits, hidden = self.preprocess(obs, state=kwargs.get("state", None))
+        batch_size = logits.size(0)
+        if taus is None:
+            taus = torch.rand(batch_size, sample_size, dtype=logits.dtype, device=logits.device)
+        sample_size = taus.shape[1]
+        embedding = self.embed_model.hadamard(logits, taus, self.fused_embed)
+        out = self.last(embedding).view(batch_size, sample_size, -1).transpose(1, 2)
+        return (out, taus), hidden
 
 
 class ActorCritic(nn.Module):

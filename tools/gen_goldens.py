@@ -2970,13 +2970,136 @@ def gen_rainbow():
     _save("rainbow.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 30. IQNPolicy (tianshou/policy/modelfree/iqn.py) over ImplicitQuantileNetwork(Net(...))
+#     (utils/net/discrete.py:158-214): four update() calls per variant over gen_dqn's add()
+#     stream, recorded as gen_dist_dqn records QR-DQN, and besides that every torch.rand draw
+#     of an update in order (the online network at obs_next, the target network at obs_next
+#     when there is one, the online network at obs).  torch is seeded right before the first
+#     update, so a run from the recorded initial parameters and that seed draws the same
+#     stream.  Every greedy selection's f64 top-two relative gap is asserted >= 1e-6.
+# --------------------------------------------------------------------------------------
+IQN_NET = dict(feature_hidden=[16], feature_out=16, head_hidden=[16], num_cosines=12)
+IQN_VARIANTS = {
+    "target": dict(freq=2, n_step=1, bs=32, optim="adam", N=8, M=8),
+    "uneven": dict(freq=3, n_step=3, bs=33, optim="adam", N=5, M=7),
+    "notarget": dict(freq=0, n_step=2, bs=17, optim="adam", N=8, M=8),
+    "per": dict(freq=2, n_step=1, bs=32, optim="adam", N=8, M=8, per=True),
+    "rms": dict(freq=3, n_step=1, bs=32, optim="rms", N=8, M=8),
+}
+IQN_UPDATES = 4
+IQN_INIT_SEED, IQN_SAMPLE_SEED, IQN_DRAW_SEED = 11, 8, 5
+
+
+def gen_iqn():
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import IQNPolicy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.discrete import ImplicitQuantileNetwork
+    out = {}
+    E, S, D, A = DQN_E, DQN_S, DQN_D, DQN_A
+    adds = _dqn_adds(np.random.default_rng(41))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    rand = torch.rand
+    for tag, v in IQN_VARIANTS.items():
+        p = tag + "_"
+        if v.get("per"):
+            buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+        else:
+            buf = VectorReplayBuffer(E * S, E)
+        for a in adds:
+            buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                    buffer_ids=a["ids"])
+        torch.manual_seed(IQN_INIT_SEED)
+        feature = Net(D, IQN_NET["feature_out"], hidden_sizes=IQN_NET["feature_hidden"])
+        net = ImplicitQuantileNetwork(feature, A, hidden_sizes=IQN_NET["head_hidden"],
+                                      num_cosines=IQN_NET["num_cosines"])
+        if v["optim"] == "rms":
+            optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+        else:
+            optim = torch.optim.Adam(net.parameters(), lr=1e-3)
+        policy = IQNPolicy(net, optim, discount_factor=0.97, sample_size=16,
+                           online_sample_size=v["N"], target_sample_size=v["M"],
+                           estimation_step=v["n_step"], target_update_freq=v["freq"])
+        if "state_keys" not in out:  # every variant starts from these weights
+            out.update({"init_" + k: t.detach().numpy().copy()
+                        for k, t in net.state_dict().items()})
+            out["state_keys"] = np.array(json.dumps(list(net.state_dict())))
+            out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+                np.asarray(buf.last_index)
+        process_fn, learn, forward = policy.process_fn, policy.learn, policy.forward
+        seen, gaps, draws = [], [], []
+
+        def rec_rand(*a, **kw_):
+            t = rand(*a, **kw_)
+            draws.append(t.detach().numpy().copy())
+            return t
+
+        def rec_forward(batch, state=None, model="model", input="obs", **kw_):
+            res = forward(batch, state, model=model, input=input, **kw_)
+            if model == "model" and input == "obs_next":
+                gaps.append(_top2_gap(res.logits.detach().double().mean(2).numpy()))
+            return res
+
+        def rec_process(batch, buffer, indices):
+            batch = process_fn(batch, buffer, indices)
+            seen.append(dict(indices=np.array(indices, copy=True),
+                             returns=batch.returns.detach().numpy().copy()))
+            if hasattr(batch, "weight"):
+                seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+            return batch
+
+        def rec_learn(batch, **kw_):
+            res = learn(batch, **kw_)
+            seen[-1]["out_weight"] = batch.weight.detach().numpy().copy()
+            return res
+
+        policy.process_fn, policy.learn, policy.forward = rec_process, rec_learn, rec_forward
+        np.random.seed(IQN_SAMPLE_SEED)
+        torch.manual_seed(IQN_DRAW_SEED)
+        torch.rand = rec_rand
+        try:
+            for u in range(IQN_UPDATES):
+                del draws[:]
+                res = policy.update(v["bs"], buf)
+                q = p + f"u{u}_"
+                out[q + "loss"] = np.array(res["loss"])
+                for k, a in seen[u].items():
+                    out[q + k] = a
+                want = [(v["bs"], v["N"])] + ([(v["bs"], v["M"])] if v["freq"] else []) + \
+                    [(v["bs"], v["N"])]
+                assert [d.shape for d in draws] == want, (tag, [d.shape for d in draws])
+                for i, d in enumerate(draws):
+                    out[q + f"draw{i}"] = d
+                out.update({q + "param_" + k: t.detach().numpy().copy()
+                            for k, t in net.state_dict().items()})
+                if v.get("per"):
+                    out[q + "leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+        finally:
+            torch.rand = rand
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+        assert len(gaps) == IQN_UPDATES, (tag, len(gaps))
+        out[p + "top2_gap"] = np.array(min(gaps))
+        print(tag, "top-two gap", min(gaps))
+        assert min(gaps) >= 1e-6, (tag, min(gaps))
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=E, S=S, D=D, A=A, gamma=0.97, net=IQN_NET, sample_size=16, updates=IQN_UPDATES,
+        init_seed=IQN_INIT_SEED, seed=IQN_SAMPLE_SEED, draw_seed=IQN_DRAW_SEED,
+        variants=IQN_VARIANTS)))
+    _save("iqn.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
-                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow"]
+                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -2987,6 +3110,6 @@ if __name__ == "__main__":
                  offpolicy_trainer=gen_offpolicy_trainer,
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
-                 redq=gen_redq, rainbow=gen_rainbow)
+                 redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn)
     for w in which:
         table[w]()
