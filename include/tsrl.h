@@ -951,6 +951,50 @@ int tsrl_iqn_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn, const int64
                           float* prio, double* partials, float* loss, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * FQFPolicy / FractionProposalNetwork / FullQuantileFunction (tianshou/policy/modelfree/fqf.py,
+ * utils/net/discrete.py:217-316), csrc/dqn_dist.hip.  One workgroup per batch row, per-row
+ * arithmetic in f64 rounded once per output, layouts and strides as the tsrl_iqn_* calls.  The
+ * quantile Huber loss of fqf.py:130-140 is tsrl_iqn_loss_fwd_bwd with taus = tau_hats, m = n.
+ * tsrl_fqf_propose_fwd: discrete.py:241-249 from the proposal logits [b, n], 2 <= n <=
+ *   TSRL_DIST_MAX_N.  logp[r][k] = l_k - logsumexp(l) ([b, n], kept for the backward), p_k =
+ *   exp(logp_k); taus[r][0] = 0 exactly and taus[r][i] = sum_{k < i} p_k ([b, n + 1]): f64 prefix
+ *   sums in index order, each rounded once (beyond 256 fractions the row is cut into 256 runs
+ *   whose sums are chained in index order; a prefix never exceeds the next one); tau_hats[r][i]
+ *   = (taus[i] + taus[i + 1]) / 2 in f32 from the rounded taus, which is what torch computes from
+ *   them ([b, n]); entropies[r] = -sum_k p_k max(logp_k, -FLT_MAX).  A -inf logit contributes 0
+ *   everywhere; a NaN logit makes the row's outputs NaN except taus[r][0].  b == 0 launches
+ *   nothing.
+ * tsrl_fqf_select: tsrl_iqn_select with q_out[r][a] = sum_i (taus[r][i + 1] - taus[r][i]) *
+ *   sel[r][a][i] (fqf.py:103-107; the difference in f32, product and sum f64, rounded once) in
+ *   place of the mean; taus [b, n + 1]; eval, when given, is [b, A, n] too.
+ * tsrl_fqf_fraction_loss_fwd_bwd: fqf.py:142-164 and its backward to the proposal logits.  curr
+ *   [b, A, n] with strides (sa, sn), qtau [b, A, n - 1] with strides (ta, tn) (the quantiles at
+ *   taus[:, 1:-1]), act [b], taus [b, n + 1], logp [b, n], entropies [b].  With a = act[r],
+ *   h_i = curr[r][a][i] and q_i = qtau[r][a][i - 1] (i = 1..n-1): G_i = (q_i > L_i ? v1 : -v1) +
+ *   (q_i < R_i ? v2 : -v2), v1 = q_i - h_{i-1}, v2 = q_i - h_i, L_1 = h_0 else L_i = q_{i-1},
+ *   R_{n-1} = h_{n-1} else R_i = q_{i+1}; every operation of G in f32, so G is torch's
+ *   gradient_of_taus bit for bit (grad_taus_out [b, n - 1], may be NULL, receives it).
+ *   losses[0] = mean_r sum_i G_i taus[r][i], losses[1] = mean_r entropies[r], f64 sums in row
+ *   order (partials: 2 * b doubles, needed when b > 1).  g_logits [b, n] is the gradient of
+ *   losses[0] - ent_coef * losses[1]: with S_k = (1/b) sum_{i > k} G_i, p_k = exp(logp_k) and
+ *   H = entropies[r], g_logits[r][k] = p_k (S_k - sum_j p_j S_j) + (ent_coef / b) p_k (logp_k +
+ *   H), and 0 where p_k == 0.  An act outside [0, A) gives NaN losses and a NaN row of g_logits
+ *   and grad_taus_out.  2 <= n <= TSRL_DIST_MAX_N.
+ * ------------------------------------------------------------------------------- */
+int tsrl_fqf_propose_fwd(const float* logits, int64_t b, int64_t n, float* taus, float* tau_hats,
+                         float* entropies, float* logp, void* stream);
+int tsrl_fqf_select(const float* sel, int64_t sel_sa, int64_t sel_sn, const float* eval,
+                    int64_t eval_sa, int64_t eval_sm, const float* taus, int64_t b,
+                    int64_t num_actions, int64_t n, float* q_out, int64_t* act_out,
+                    float* row_out, void* stream);
+int tsrl_fqf_fraction_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn, const float* qtau,
+                                   int64_t ta, int64_t tn, const int64_t* act, const float* taus,
+                                   const float* logp, const float* entropies, double ent_coef,
+                                   int64_t b, int64_t num_actions, int64_t n, float* g_logits,
+                                   float* grad_taus_out, double* partials, float* losses,
+                                   void* stream);
+
+/* ---------------------------------------------------------------------------------
  * RainbowPolicy (tianshou/policy/modelfree/rainbow.py): NoisyLinear (utils/net/discrete.py:
  * 319-394) and the dueling combine (utils/net/common.py:276-284), csrc/noisy.hip.  All tensors
  * f32 and 4-byte aligned unless noted; no call synchronises or allocates, so each can be

@@ -8,11 +8,17 @@
 //                 (qrdqn.py:82-93) without its [b, N, N] tensors;
 //   iqn_*:        IQNPolicy's siblings of dist_select and qr_loss for N online against M target
 //                 quantiles at per-row fractions, read through strides, and the cosine
-//                 embedding of ImplicitQuantileNetwork with its backward (further down).
+//                 embedding of ImplicitQuantileNetwork with its backward (further down);
+//   fqf_*:        FQFPolicy's proposal forward (softmax, cumulative fractions, midpoints,
+//                 entropy), its select (a template branch of iqn_select) and the fraction loss
+//                 with its gradient to the proposal logits (at the end).
 // One workgroup per batch row, lanes over the N atoms (a loop when N exceeds the workgroup):
 // b is 32 to a few hundred, so the grid is b workgroups of one to four waves and the cost is
 // launch latency.  Sums are f64 in a fixed order (lanes by xor butterfly, waves in wave order,
 // rows in row order by the fold launch): bit-identical between runs, no atomics.
+#include <float.h>
+
+#include "loss_sum.h"
 #include "tsrl_common.h"
 
 namespace tsrl {
@@ -354,10 +360,13 @@ __global__ __launch_bounds__(TPB) void iqn_gb_fold_kernel(const double* __restri
 }
 
 // dist_select_kernel with strides, a mean only, and an eval of its own column count M.
+// FRAC (FQFPolicy, fqf.py:103-107): instead of the mean, the row's own weights taus[r][i + 1] -
+// taus[r][i] (taus [b, N + 1]; the difference in f32 as torch forms it, product and sum f64).
+template <bool FRAC>
 __global__ __launch_bounds__(TPB) void iqn_select_kernel(
     const float* __restrict__ sel, int64_t sA, int64_t sN, const float* __restrict__ eval,
-    int64_t eA, int64_t eM, int64_t A, int64_t N, int64_t M, float* __restrict__ q_out,
-    int64_t* __restrict__ act_out, float* __restrict__ row_out) {
+    int64_t eA, int64_t eM, const float* __restrict__ taus, int64_t A, int64_t N, int64_t M,
+    float* __restrict__ q_out, int64_t* __restrict__ act_out, float* __restrict__ row_out) {
     __shared__ float s_best[NW];
     __shared__ int64_t s_arg[NW];
     __shared__ int64_t s_act;
@@ -370,9 +379,15 @@ __global__ __launch_bounds__(TPB) void iqn_select_kernel(
     for (int64_t a = wv; a < A; a += NW) {
         const float* x = row + a * sA;
         double acc = 0.0;
-        for (int64_t n = lane; n < N; n += kWave) acc += (double)x[n * sN];
+        if (FRAC) {
+            const float* tr = taus + r * (N + 1);
+            for (int64_t n = lane; n < N; n += kWave)
+                acc += (double)(tr[n + 1] - tr[n]) * (double)x[n * sN];
+        } else {
+            for (int64_t n = lane; n < N; n += kWave) acc += (double)x[n * sN];
+        }
         acc = wave_sum(acc);
-        const float q = (float)(acc * inv_n);
+        const float q = (float)(FRAC ? acc : acc * inv_n);
         if (q_out && lane == 0) q_out[r * A + a] = q;
         if (arg < 0 || beats_at(q, a, best, arg)) {
             best = q;
@@ -477,6 +492,187 @@ __global__ __launch_bounds__(TPB) void iqn_loss_kernel(
 // Either layout of a [b, A, N] view whose batch rows are A * N elements long.
 inline bool row_strides_ok(int64_t sa, int64_t sn, int64_t A, int64_t N) {
     return (sa == N && sn == 1) || (sa == 1 && sn == A);
+}
+
+// -- FQFPolicy (tianshou/policy/modelfree/fqf.py, utils/net/discrete.py:217-316) -----------------
+// A row's N values are cut into blockDim.x chunks of `per` consecutive elements, one per thread.
+// The chunk sums are chained in index order by thread 0 and every thread then walks its own chunk
+// in index order from its chain value, so with N <= blockDim.x the whole sum is in index order,
+// and beyond that a prefix never exceeds the next one (a chunk's running sum ends at the value
+// the chain carried on).  `tot` is the thread's chunk sum; chain: blockDim.x + 1 doubles.
+// Forward: returns the sum of the chunks before this one, chain[blockDim.x] the row's sum.
+__device__ __forceinline__ double chain_before(double tot, double* chain) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __syncthreads();  // chain may still be read from an earlier call
+    chain[t] = tot;
+    __syncthreads();
+    if (t == 0) {
+        double run = 0.0;
+        for (int i = 0; i < nt; ++i) {
+            const double c = chain[i];
+            chain[i] = run;
+            run += c;
+        }
+        chain[nt] = run;
+    }
+    __syncthreads();
+    return chain[t];
+}
+
+// Backward: returns the sum of the chunks after this one.
+__device__ __forceinline__ double chain_after(double tot, double* chain) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __syncthreads();
+    chain[t] = tot;
+    __syncthreads();
+    if (t == 0) {
+        double run = 0.0;
+        for (int i = nt - 1; i >= 0; --i) {
+            const double c = chain[i];
+            chain[i] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    return chain[t];
+}
+
+// discrete.py:241-249 for one row.  LDS: p as N doubles, then the rounded taus as N + 1 floats.
+// max and logsumexp first, then logp_k = l_k - lse, p_k = exp(logp_k), the entropy, and the
+// prefix sums of p by chain_before.  A NaN logit makes the maximum NaN and with it everything
+// but taus[0].
+__global__ __launch_bounds__(TPB) void fqf_propose_kernel(
+    const float* __restrict__ logits, int64_t N, float* __restrict__ taus,
+    float* __restrict__ tau_hats, float* __restrict__ entropies, float* __restrict__ logp_out) {
+    extern __shared__ double lds_d[];
+    __shared__ double red[NW];
+    __shared__ double chain[TPB + 1];
+    __shared__ float s_max[NW];
+    double* p = lds_d;
+    float* tau32 = reinterpret_cast<float*>(lds_d + N);
+    const int t = threadIdx.x, nt = blockDim.x, lane = t & (kWave - 1), wv = t / kWave;
+    const int64_t r = blockIdx.x;
+    const float* l = logits + r * N;
+    float m = -INFINITY;
+    bool nan = false;
+    for (int64_t k = t; k < N; k += nt) {
+        const float v = l[k];
+        nan |= v != v;
+        m = fmaxf(m, v);
+    }
+    if (nan) m = NAN;
+    for (int off = 32; off > 0; off >>= 1) {
+        const float o = __shfl_xor(m, off, kWave);
+        m = (m != m || o != o) ? NAN : fmaxf(m, o);
+    }
+    if (lane == 0) s_max[wv] = m;
+    __syncthreads();
+    m = s_max[0];
+    for (int i = 1; i < (nt + kWave - 1) / kWave; ++i) {
+        const float o = s_max[i];
+        m = (m != m || o != o) ? NAN : fmaxf(m, o);
+    }
+    double se = 0.0;
+    for (int64_t k = t; k < N; k += nt) se += exp((double)l[k] - (double)m);
+    const double lse = (double)m + log(block_sum(se, red));
+    double ent = 0.0;
+    for (int64_t k = t; k < N; k += nt) {
+        const double lp = (double)l[k] - lse;
+        const double pk = exp(lp);
+        p[k] = pk;
+        logp_out[r * N + k] = (float)lp;
+        // Categorical.entropy clamps logp at the lowest finite f32: a -inf logit gives 0 * that
+        ent += pk * (lp < -(double)FLT_MAX ? -(double)FLT_MAX : lp);
+    }
+    const double es = block_sum(ent, red);  // its barriers also publish p
+    if (t == 0) entropies[r] = (float)(-es);
+    const int64_t per = (N + nt - 1) / nt;
+    const int64_t lo = (int64_t)t * per, hi = lo + per < N ? lo + per : N;
+    double tot = 0.0;
+    for (int64_t k = lo; k < hi; ++k) tot += p[k];
+    double run = chain_before(tot, chain);
+    for (int64_t k = lo; k < hi; ++k) {
+        tau32[k] = k == 0 ? 0.0f : (float)run;  // taus[0] is 0 whatever the row holds
+        run += p[k];
+    }
+    if (t == 0) tau32[N] = (float)chain[nt];
+    __syncthreads();
+    float* tau_row = taus + r * (N + 1);
+    for (int64_t k = t; k <= N; k += nt) tau_row[k] = tau32[k];
+    for (int64_t k = t; k < N; k += nt) tau_hats[r * N + k] = (tau32[k] + tau32[k + 1]) / 2.0f;
+}
+
+// fqf.py:142-164 and its backward to the proposal logits for one row.  LDS: G as N floats (G[0]
+// unused).  Thread i forms G_i in f32 as torch does; S_k, the suffix sums of G, by chain_after.
+__global__ __launch_bounds__(TPB) void fqf_fraction_kernel(
+    const float* __restrict__ curr, int64_t sA, int64_t sN, const float* __restrict__ qtau,
+    int64_t tA, int64_t tN, const int64_t* __restrict__ act, const float* __restrict__ taus,
+    const float* __restrict__ logp, const float* __restrict__ entropies, double ent_coef,
+    int64_t b, int64_t A, int64_t N, float* __restrict__ g_logits,
+    float* __restrict__ grad_taus_out, double* __restrict__ partials, MeanLosses<2> fin) {
+    extern __shared__ float lds[];
+    __shared__ double chain[TPB + 1];
+    const int t = threadIdx.x, nt = blockDim.x;
+    const int64_t r = blockIdx.x;
+    const int64_t a = act[r];
+    float* G = lds;
+    double term[2] = {0.0, 0.0};
+    double s[2];
+    if (a < 0 || a >= A) {
+        for (int64_t k = t; k < N; k += nt) g_logits[r * N + k] = NAN;
+        if (grad_taus_out)
+            for (int64_t i = t; i < N - 1; i += nt) grad_taus_out[r * (N - 1) + i] = NAN;
+        if (t == 0) term[0] = term[1] = (double)NAN;
+        block_sums<2>(term, s);
+        losses_or_partials<2>(s, partials, fin);
+        return;
+    }
+    const float* h = curr + r * A * N + a * sA;
+    const float* q = qtau + r * A * (N - 1) + a * tA;
+    const float* tau_row = taus + r * (N + 1);
+    for (int64_t i = 1 + t; i < N; i += nt) {
+        const float qi = q[(i - 1) * tN];
+        const float left = i == 1 ? h[0] : q[(i - 2) * tN];
+        const float right = i == N - 1 ? h[(N - 1) * sN] : q[i * tN];
+        const float v1 = qi - h[(i - 1) * sN], v2 = qi - h[i * sN];
+        const float g = (qi > left ? v1 : -v1) + (qi < right ? v2 : -v2);
+        G[i] = g;
+        if (grad_taus_out) grad_taus_out[r * (N - 1) + i - 1] = g;
+        term[0] += (double)g * (double)tau_row[i];
+    }
+    if (t == 0) {
+        G[0] = 0.0f;
+        term[1] = (double)entropies[r];
+    }
+    block_sums<2>(term, s);  // its barrier also publishes G
+    losses_or_partials<2>(s, partials, fin);
+    // S_k = (1 / b) sum_{i > k} G_i over this thread's chunk of k, last to first
+    const int64_t per = (N + nt - 1) / nt;
+    const int64_t lo = (int64_t)t * per, hi = lo + per < N ? lo + per : N;
+    double tot = 0.0;
+    for (int64_t k = hi - 1; k >= lo; --k) tot += (double)G[k];
+    // sum_{i > k} G_i = (the chunks after) + (this chunk's G after k); the chain is over G_k
+    // themselves, so the walk adds G_k after using the sum
+    const double after = chain_after(tot, chain);
+    const double inv_b = 1.0 / (double)b;
+    const float* lp_row = logp + r * N;
+    double run = after, ps = 0.0;
+    for (int64_t k = hi - 1; k >= lo; --k) {
+        const double pk = exp((double)lp_row[k]);
+        if (pk != 0.0) ps += pk * (run * inv_b);
+        run += (double)G[k];
+    }
+    __shared__ double red[NW];
+    const double sbar = block_sum(ps, red);
+    const double H = (double)entropies[r], ec = ent_coef * inv_b;
+    run = after;
+    for (int64_t k = hi - 1; k >= lo; --k) {
+        const double lp = (double)lp_row[k];
+        const double pk = exp(lp);
+        g_logits[r * N + k] =
+            pk == 0.0 ? 0.0f : (float)(pk * (run * inv_b - sbar) + ec * pk * (lp + H));
+        run += (double)G[k];
+    }
 }
 
 }  // namespace
@@ -598,9 +794,9 @@ extern "C" int tsrl_iqn_select(const float* sel, int64_t sel_sa, int64_t sel_sn,
                    "[b, M, A] view");
     if (b == 0) return 0;
     TSRL_CHECK_ARG(sel, "tsrl_iqn_select: null pointer");
-    hipLaunchKernelGGL(iqn_select_kernel, dim3((unsigned)b), dim3(TPB), 0, as_stream(stream), sel,
-                       sel_sa, sel_sn, eval, eval_sa, eval_sm, num_actions, n, m, q_out, act_out,
-                       row_out);
+    hipLaunchKernelGGL(iqn_select_kernel<false>, dim3((unsigned)b), dim3(TPB), 0,
+                       as_stream(stream), sel, sel_sa, sel_sn, eval, eval_sa, eval_sm,
+                       (const float*)nullptr, num_actions, n, m, q_out, act_out, row_out);
     TSRL_LAUNCH_CHECK("tsrl_iqn_select");
     return 0;
 }
@@ -627,6 +823,73 @@ extern "C" int tsrl_iqn_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn,
         hipLaunchKernelGGL(dist_fold_kernel, dim3(1), dim3(kWave), 0, as_stream(stream),
                            partials, b, loss);
         TSRL_LAUNCH_CHECK("tsrl_iqn_loss_fwd_bwd (fold)");
+    }
+    return 0;
+}
+
+extern "C" int tsrl_fqf_propose_fwd(const float* logits, int64_t b, int64_t n, float* taus,
+                                    float* tau_hats, float* entropies, float* logp,
+                                    void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && b < ((int64_t)1 << 31) && n >= 2 && n <= kMaxN,
+                   "tsrl_fqf_propose_fwd: need 0 <= b < 2^31 and 2 <= n <= %d", (int)kMaxN);
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(logits && taus && tau_hats && entropies && logp,
+                   "tsrl_fqf_propose_fwd: null pointer");
+    hipLaunchKernelGGL(fqf_propose_kernel, dim3((unsigned)b), dim3(atom_threads(n)),
+                       (size_t)n * sizeof(double) + (size_t)(n + 1) * sizeof(float),
+                       as_stream(stream), logits, n, taus, tau_hats, entropies, logp);
+    TSRL_LAUNCH_CHECK("tsrl_fqf_propose_fwd");
+    return 0;
+}
+
+extern "C" int tsrl_fqf_select(const float* sel, int64_t sel_sa, int64_t sel_sn,
+                               const float* eval, int64_t eval_sa, int64_t eval_sm,
+                               const float* taus, int64_t b, int64_t num_actions, int64_t n,
+                               float* q_out, int64_t* act_out, float* row_out, void* stream) {
+    TSRL_CHECK_ARG(b >= 0 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 1,
+                   "tsrl_fqf_select: need 0 <= b < 2^31, num_actions >= 1 and n >= 1");
+    TSRL_CHECK_ARG(row_strides_ok(sel_sa, sel_sn, num_actions, n),
+                   "tsrl_fqf_select: sel strides (%lld, %lld) are neither [b, A, N] nor the "
+                   "[b, N, A] view", (long long)sel_sa, (long long)sel_sn);
+    TSRL_CHECK_ARG(!eval || row_strides_ok(eval_sa, eval_sm, num_actions, n),
+                   "tsrl_fqf_select: eval needs the strides of [b, A, N] or its [b, N, A] view");
+    if (b == 0) return 0;
+    TSRL_CHECK_ARG(sel && taus, "tsrl_fqf_select: null pointer");
+    hipLaunchKernelGGL(iqn_select_kernel<true>, dim3((unsigned)b), dim3(TPB), 0,
+                       as_stream(stream), sel, sel_sa, sel_sn, eval, eval_sa, eval_sm, taus,
+                       num_actions, n, n, q_out, act_out, row_out);
+    TSRL_LAUNCH_CHECK("tsrl_fqf_select");
+    return 0;
+}
+
+extern "C" int tsrl_fqf_fraction_loss_fwd_bwd(const float* curr, int64_t sa, int64_t sn,
+                                              const float* qtau, int64_t ta, int64_t tn,
+                                              const int64_t* act, const float* taus,
+                                              const float* logp, const float* entropies,
+                                              double ent_coef, int64_t b, int64_t num_actions,
+                                              int64_t n, float* g_logits, float* grad_taus_out,
+                                              double* partials, float* losses, void* stream) {
+    TSRL_CHECK_ARG(b >= 1 && b < ((int64_t)1 << 31) && num_actions >= 1 && n >= 2 && n <= kMaxN,
+                   "tsrl_fqf_fraction_loss_fwd_bwd: need 1 <= b < 2^31, num_actions >= 1, "
+                   "2 <= n <= %d", (int)kMaxN);
+    TSRL_CHECK_ARG(row_strides_ok(sa, sn, num_actions, n) &&
+                       row_strides_ok(ta, tn, num_actions, n - 1),
+                   "tsrl_fqf_fraction_loss_fwd_bwd: strides (%lld, %lld) of curr or (%lld, %lld) "
+                   "of qtau are neither [b, A, .] nor the [b, ., A] view", (long long)sa,
+                   (long long)sn, (long long)ta, (long long)tn);
+    TSRL_CHECK_ARG(curr && qtau && act && taus && logp && entropies && g_logits && losses &&
+                       (b == 1 || partials),
+                   "tsrl_fqf_fraction_loss_fwd_bwd: null pointer");
+    const MeanLosses<2> fin{(double)b, 1.0f, losses, nullptr};
+    hipLaunchKernelGGL(fqf_fraction_kernel, dim3((unsigned)b), dim3(TPB),
+                       (size_t)n * sizeof(float), as_stream(stream), curr, sa, sn, qtau, ta, tn,
+                       act, taus, logp, entropies, ent_coef, b, num_actions, n, g_logits,
+                       grad_taus_out, partials, fin);
+    TSRL_LAUNCH_CHECK("tsrl_fqf_fraction_loss_fwd_bwd");
+    if (b > 1) {
+        hipLaunchKernelGGL((loss_fold_kernel<2, MeanLosses<2>>), dim3(1), dim3(kWave), 0,
+                           as_stream(stream), partials, b, fin);
+        TSRL_LAUNCH_CHECK("tsrl_fqf_fraction_loss_fwd_bwd (fold)");
     }
     return 0;
 }

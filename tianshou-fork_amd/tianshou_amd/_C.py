@@ -242,6 +242,11 @@ _SIGS = {
                          _p], ctypes.c_int),
     "tsrl_iqn_loss_fwd_bwd": ([_p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p,
                                _p, _p, _p], ctypes.c_int),
+    "tsrl_fqf_propose_fwd": ([_p, _i64, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_fqf_select": ([_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p],
+                        ctypes.c_int),
+    "tsrl_fqf_fraction_loss_fwd_bwd": ([_p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _d, _i64,
+                                        _i64, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_noisy_eps": ([_p, _i64, _p, _p], ctypes.c_int),
     "tsrl_noisy_weights": ([_p, _i64, _i64, _p], ctypes.c_int),
     "tsrl_noisy_grads": ([_p, _p, _p, _p, _i64, _i64, _p, _p, _p], ctypes.c_int),

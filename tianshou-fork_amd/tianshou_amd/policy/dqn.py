@@ -21,7 +21,9 @@ The distributional subclasses C51Policy (policy/c51.py) and QRDQNPolicy (policy/
 the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_weight``,
 ``_before_forward``, ``_forward_q``, ``_fused_loss``) and reuse the flat storage, the sync and
 the graph replay as they are; RainbowPolicy (policy/rainbow.py) is C51Policy over NoisyLinear
-layers and IQNPolicy (policy/iqn.py) QRDQNPolicy over ImplicitQuantileNetwork.
+layers, IQNPolicy (policy/iqn.py) QRDQNPolicy over ImplicitQuantileNetwork, and FQFPolicy
+(policy/fqf.py) adds a second network with a flat optimiser of its own (``_flats``,
+``_loss_out``, ``_learn_result``).
 """
 from copy import deepcopy
 from typing import Any, Dict, Optional, Union
@@ -301,7 +303,8 @@ class DQNPolicy(BasePolicy):
             extra = self._learn_inputs(batch)
             out = None
             if fa is not None:
-                fa.set_lr()
+                for f in self._flats(fa):
+                    f.set_lr()
                 if self._warm and net_in is obs and self._graph_ok(net_in, n) and \
                         all(isinstance(e, torch.Tensor) and e.is_cuda for e in extra):
                     out = self._graph_step(fa, net_in, act, returns, w, *extra)
@@ -311,7 +314,7 @@ class DQNPolicy(BasePolicy):
             self._warm = True
         batch.weight = td.detach()  # prio-buffer
         self._iter += 1
-        return {"loss": loss.item()}
+        return self._learn_result(loss)
 
     def _learn_torch(self, batch: Batch, weight):
         """The reference's op sequence as written (dqn.py:170-186), on whatever device the
@@ -340,6 +343,19 @@ class DQNPolicy(BasePolicy):
 
     def _returns_rows(self, batch: Batch, dev, n: int) -> torch.Tensor:
         return f32_rows(batch.returns, dev, n)
+
+    def _flats(self, fa: FlatAdam) -> tuple:
+        """Every flat optimiser storage one update steps (FQFPolicy adds its proposal
+        network's)."""
+        return (fa,)
+
+    def _loss_out(self, dev) -> torch.Tensor:
+        """The static loss output of a learn graph (FQFPolicy's holds its four scalars)."""
+        return torch.empty((), dtype=torch.float32, device=dev)
+
+    def _learn_result(self, loss: torch.Tensor) -> Dict[str, float]:
+        """learn()'s dictionary from the device loss: the update's one host read."""
+        return {"loss": loss.item()}
 
     def _loss_weight(self, weight, dev, n: int) -> Optional[torch.Tensor]:
         return None if weight is None or self._clip_loss_grad else f32_rows(weight, dev, n)
@@ -396,15 +412,17 @@ class DQNPolicy(BasePolicy):
         static copies of obs / act / returns / weight (and a subclass's extra inputs) feed it,
         the loss and the TD errors come out of static outputs (flat_learn.replay_learn_graph).
         None if the capture failed (this and every later update then run eagerly)."""
-        fa.bind_grads()
-        addr = (fa.flat_grad.data_ptr(), tuple(p.data_ptr() for p in fa.params)) + \
-            self._graph_addrs()
+        addr = ()
+        for f in self._flats(fa):
+            f.bind_grads()
+            addr += (f.flat_grad.data_ptr(), tuple(p.data_ptr() for p in f.params))
+        addr += self._graph_addrs()
         key = (len(act), tuple(obs.shape), obs.dtype, weight is not None,
                tuple((tuple(e.shape), e.dtype) for e in extra))
         out = replay_learn_graph(
             self._learn_graphs, key, addr, (obs, act, returns, weight, *extra),
             lambda: (torch.empty(len(act), dtype=torch.float32, device=act.device),
-                     torch.empty((), dtype=torch.float32, device=act.device)),
+                     self._loss_out(act.device)),
             lambda s, td, loss: self._step(fa, s[0], Batch(), *s[1:], td_out=td, loss_out=loss),
             self._capture)
         if out is None:

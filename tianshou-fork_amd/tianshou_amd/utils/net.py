@@ -2,8 +2,8 @@
 tianshou 0.5.1 checkpoints (utils/net/common.py:56-285, continuous.py:87-235,
 discrete.py:12-121, 319-394).  The GEMMs run through PyTorch-ROCm (hipBLASLt) on the GPU;
 NoisyLinear's effective parameters, its sigma gradients and the dueling combine are the kernels
-of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd
-(csrc/dqn_dist.hip)."""
+of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd and
+FractionProposalNetwork's forward tsrl_fqf_propose_fwd (csrc/dqn_dist.hip)."""
 import contextlib
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
 
@@ -780,6 +780,124 @@ class ImplicitQuantileNetwork(DiscreteCritic):
         embedding = self.embed_model.hadamard(logits, taus, self.fused_embed)
         out = self.last(embedding).view(batch_size, sample_size, -1).transpose(1, 2)
         return (out, taus), hidden
+
+
+class _FQFProposeFn(torch.autograd.Function):
+    """discrete.py:241-249 from the proposal logits [b, N] as one tsrl_fqf_propose_fwd launch:
+    returns (taus [b, N + 1], tau_hats [b, N], entropies [b], logp [b, N]).  The backward is the
+    analytic one for any incoming g_taus and g_entropies (cumsum, softmax, entropy); tau_hats are
+    detached as in the reference and logp is the kernel's by-product for
+    tsrl_fqf_fraction_loss_fwd_bwd."""
+
+    @staticmethod
+    def forward(ctx, logits):
+        x = logits.detach().float().contiguous()
+        if x.dim() != 2:
+            raise ValueError(f"_FQFProposeFn: need [b, N] logits, got {tuple(x.shape)}")
+        b, N = x.shape
+        dev = x.device
+        taus = torch.empty(b, N + 1, dtype=torch.float32, device=dev)
+        tau_hats = torch.empty(b, N, dtype=torch.float32, device=dev)
+        entropies = torch.empty(b, dtype=torch.float32, device=dev)
+        logp = torch.empty(b, N, dtype=torch.float32, device=dev)
+        _C.check(_C.lib().tsrl_fqf_propose_fwd(
+            _C.ptr(x), b, N, _C.ptr(taus), _C.ptr(tau_hats), _C.ptr(entropies), _C.ptr(logp),
+            _C.stream_ptr(dev)), "tsrl_fqf_propose_fwd")
+        ctx.save_for_backward(logp, entropies)
+        ctx.in_dtype = logits.dtype
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(tau_hats, logp)
+        return taus, tau_hats, entropies, logp
+
+    @staticmethod
+    def backward(ctx, g_taus, g_hats, g_ent, g_logp):
+        logp, entropies = ctx.saved_tensors
+        # in f64 as the kernels' per-row arithmetic, rounded once: with one fraction near 1 the
+        # softmax backward cancels (in f32 it missed the 4 x torch bound at N = 2)
+        logp = logp.double()
+        p = logp.exp()
+        g = None
+        if g_taus is not None:
+            # taus[i] = sum_{k < i} p_k: dL/dp_k = sum_{i > k} g_taus[i], then the softmax
+            g_p = g_taus[:, 1:].double().flip(1).cumsum(1).flip(1)
+            g = p * (g_p - (p * g_p).sum(1, keepdim=True))
+        if g_ent is not None:
+            # dH/dl_k = -p_k (logp_k + H); a p_k of exactly 0 (logp -inf) contributes 0
+            t = torch.where(p == 0, torch.zeros_like(p),
+                            p * (logp + entropies.double().unsqueeze(1)))
+            g_e = -g_ent.double().unsqueeze(1) * t
+            g = g_e if g is None else g + g_e
+        return None if g is None else g.to(ctx.in_dtype)
+
+
+class FractionProposalNetwork(nn.Module):
+    """FQF's fraction proposal network (utils/net/discrete.py:217-249): one Linear named ``net``
+    with the reference's initialiser in its order, so a seeded CPU construction reproduces its
+    weights.  ``forward`` returns (taus [b, N + 1], tau_hats [b, N], entropies [b]).  On a HIP
+    device with f32 inputs and N <= _C.DIST_MAX_N the softmax, cumsum, pad, midpoints and
+    entropy are one tsrl_fqf_propose_fwd launch (``_FQFProposeFn``) and the Linear's gradients
+    come from ``_linear_grads``; elsewhere, and with ``fused = False`` (``FQFPolicy.fused``
+    sets it), the reference's torch lines run."""
+
+    fused = True
+
+    def __init__(self, num_fractions: int, embedding_dim: int) -> None:
+        super().__init__()
+        self.net = nn.Linear(embedding_dim, num_fractions)
+        torch.nn.init.xavier_uniform_(self.net.weight, gain=0.01)
+        torch.nn.init.constant_(self.net.bias, 0)
+        self.num_fractions = num_fractions
+        self.embedding_dim = embedding_dim
+
+    def takes_kernel(self, obs_embeddings: torch.Tensor) -> bool:
+        return self.fused and obs_embeddings.is_cuda and obs_embeddings.dim() == 2 and \
+            obs_embeddings.dtype == torch.float32 and self.net.weight.dtype == torch.float32 and \
+            2 <= self.num_fractions <= _C.DIST_MAX_N
+
+    def propose(self, obs_embeddings: torch.Tensor):
+        """The kernel path with its by-products: (logits, taus, tau_hats, entropies, logp)."""
+        logits = _LinearFn.apply(obs_embeddings, self.net.weight, self.net.bias)
+        return (logits,) + _FQFProposeFn.apply(logits)
+
+    def forward(self, obs_embeddings: torch.Tensor):
+        if self.takes_kernel(obs_embeddings):
+            return self.propose(obs_embeddings)[1:4]
+        dist = torch.distributions.Categorical(logits=self.net(obs_embeddings))
+        taus_1_N = torch.cumsum(dist.probs, dim=1)
+        taus = torch.nn.functional.pad(taus_1_N, (1, 0))
+        tau_hats = (taus[:, :-1] + taus[:, 1:]).detach() / 2.0
+        entropies = dist.entropy()
+        return taus, tau_hats, entropies
+
+
+class FullQuantileFunction(ImplicitQuantileNetwork):
+    """FQF's quantile network (utils/net/discrete.py:252-316): constructor arguments and
+    state_dict keys are ImplicitQuantileNetwork's.  ``forward`` returns ((quantiles, fractions,
+    quantiles_tau), hidden) with fractions = Batch(taus, tau_hats, entropies) proposed from the
+    detached state embedding (or handed in), quantiles at tau_hats, and quantiles_tau, under
+    no_grad and only while training, at taus[:, 1:-1].  ``want_quantiles_tau = False`` skips
+    that second pass where nobody reads it (FQFPolicy's ``_target_q``)."""
+
+    def _compute_quantiles(self, obs: torch.Tensor, taus: torch.Tensor) -> torch.Tensor:
+        batch_size, sample_size = taus.shape
+        embedding = self.embed_model.hadamard(obs, taus, self.fused_embed)
+        return self.last(embedding).view(batch_size, sample_size, -1).transpose(1, 2)
+
+    def forward(self, obs, propose_model: nn.Module, fractions=None,
+                want_quantiles_tau: bool = True, **kwargs: Any):
+        from tianshou_amd.data.batch import Batch
+        logits, hidden = self.preprocess(obs, state=kwargs.get("state", None))
+        if fractions is None:
+            taus, tau_hats, entropies = propose_model(logits.detach())
+            fractions = Batch(taus=taus, tau_hats=tau_hats, entropies=entropies)
+        else:
+            taus, tau_hats = fractions.taus, fractions.tau_hats
+        quantiles = self._compute_quantiles(logits, tau_hats)
+        quantiles_tau = None
+        if self.training and want_quantiles_tau:
+            with torch.no_grad():
+                quantiles_tau = self._compute_quantiles(logits, taus[:, 1:-1])
+        return (quantiles, fractions, quantiles_tau), hidden
 
 
 class ActorCritic(nn.Module):

@@ -3093,13 +3093,198 @@ def gen_iqn():
     _save("iqn.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 31. FQFPolicy (tianshou/policy/modelfree/fqf.py) over FullQuantileFunction(Net(...)) and
+#     FractionProposalNetwork (utils/net/discrete.py:217-316): four update() calls per variant
+#     over gen_dqn's add() stream from one recorded initial state of both networks, recorded as
+#     gen_iqn records IQN (an update has no random input), and besides that the taken action's
+#     sa_quantile_hats [bs, N] and sa_quantiles [bs, N - 1] of fqf.py:143-144.  Two conditions
+#     are asserted on the reference alone: every greedy selection's f64 top-two relative gap is
+#     >= 1e-6, and min_margin >= 1e-5, the smallest |q_i - L_i| or |q_i - R_i| of the sign tests
+#     of fqf.py:148-155 over every recorded update (they are discontinuous; each variant's
+#     sampling seed is chosen so that no comparison is a near-tie).  A third, for the Adam
+#     variants, is _fqf_conditioning's: no quantile-network parameter sits on one of Adam's
+#     sign-like first steps.  The fraction learning rate moves the proposal parameters visibly
+#     (the examples' 2.5e-9 does not).
+# --------------------------------------------------------------------------------------
+FQF_NET = dict(feature_hidden=[16], feature_out=16, head_hidden=[16], num_cosines=12)
+FQF_VARIANTS = {
+    "target": dict(freq=2, n_step=1, bs=32, optim="adam", N=8, ent_coef=10.0, seed=25),
+    "notarget": dict(freq=0, n_step=2, bs=17, optim="adam", N=8, ent_coef=0.0, seed=25),
+    "uneven": dict(freq=3, n_step=3, bs=33, optim="adam", N=5, ent_coef=10.0, seed=40),
+    "per": dict(freq=2, n_step=1, bs=32, optim="adam", N=8, ent_coef=10.0, per=True, seed=12),
+    "rms": dict(freq=3, n_step=1, bs=32, optim="rms", N=8, ent_coef=10.0, seed=21),
+}
+FQF_UPDATES = 4
+FQF_INIT_SEED = 13
+FQF_FRACTION_LR = 1e-3
+
+
+def _fqf_margin(hats, q):
+    """The smallest distance of a sign test of fqf.py:148-155 from a tie, in f64."""
+    hats, q = hats.astype(np.float64), q.astype(np.float64)
+    left = np.concatenate([hats[:, :1], q[:, :-1]], axis=1)
+    right = np.concatenate([q[:, 1:], hats[:, -1:]], axis=1)
+    return float(min(np.abs(q - left).min(), np.abs(q - right).min()))
+
+
+FQF_JITTER_ULPS = 8
+
+
+def _fqf_variant(tag, v, adds, out, jitter=None):
+    """Record one variant into ``out``; returns (top-two gap, min_margin).  ``jitter`` (a seed):
+    every initial parameter moved FQF_JITTER_ULPS f32 neighbours up or down first (gen_fqf's
+    conditioning runs)."""
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import FQFPolicy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.discrete import FractionProposalNetwork, FullQuantileFunction
+    E, S, D, A = DQN_E, DQN_S, DQN_D, DQN_A
+    p = tag + "_"
+    if v.get("per"):
+        buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+    else:
+        buf = VectorReplayBuffer(E * S, E)
+    for a in adds:
+        buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                buffer_ids=a["ids"])
+    torch.manual_seed(FQF_INIT_SEED)
+    feature = Net(D, FQF_NET["feature_out"], hidden_sizes=FQF_NET["feature_hidden"])
+    net = FullQuantileFunction(feature, A, hidden_sizes=FQF_NET["head_hidden"],
+                               num_cosines=FQF_NET["num_cosines"])
+    # every variant's proposal network has its own width: seeded on its own
+    torch.manual_seed(FQF_INIT_SEED + v["N"])
+    propose = FractionProposalNetwork(v["N"], net.input_dim)
+    if jitter is not None:
+        g = torch.Generator().manual_seed(jitter)
+        with torch.no_grad():
+            for par in list(net.parameters()) + list(propose.parameters()):
+                towards = torch.where(torch.randint(0, 2, par.shape, generator=g).bool(),
+                                      torch.full_like(par, np.inf), torch.full_like(par, -np.inf))
+                for _ in range(FQF_JITTER_ULPS):
+                    par.copy_(torch.nextafter(par, towards))
+    if v["optim"] == "rms":
+        optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+        frac_optim = torch.optim.RMSprop(propose.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+    else:
+        optim = torch.optim.Adam(net.parameters(), lr=1e-3)
+        frac_optim = torch.optim.Adam(propose.parameters(), lr=FQF_FRACTION_LR)
+    policy = FQFPolicy(net, optim, propose, frac_optim, discount_factor=0.97,
+                       num_fractions=v["N"], ent_coef=v["ent_coef"],
+                       estimation_step=v["n_step"], target_update_freq=v["freq"])
+    if "state_keys" not in out:  # every variant starts from these weights
+        out.update({"init_" + k: t.detach().numpy().copy() for k, t in net.state_dict().items()})
+        out["state_keys"] = np.array(json.dumps(list(net.state_dict())))
+        out["propose_keys"] = np.array(json.dumps(list(propose.state_dict())))
+        out["buf_lengths"], out["buf_last_index"] = np.asarray(buf._lengths), \
+            np.asarray(buf.last_index)
+    out.update({p + "pinit_" + k: t.detach().numpy().copy()
+                for k, t in propose.state_dict().items()})
+    process_fn, learn, forward = policy.process_fn, policy.learn, policy.forward
+    seen, gaps, margins = [], [], []
+
+    def rec_forward(batch, state=None, model="model", input="obs", **kw_):
+        res = forward(batch, state, model=model, input=input, **kw_)
+        taus = res.fractions.taus.detach().double()
+        if model == "model" and input == "obs_next":
+            q = ((taus[:, 1:] - taus[:, :-1]).unsqueeze(1) * res.logits.detach().double()).sum(2)
+            gaps.append(_top2_gap(q.numpy()))
+        elif model == "model" and input == "obs":  # learn()'s own forward (fqf.py:123)
+            rows, act = np.arange(len(batch.act)), np.asarray(batch.act)
+            seen[-1]["sa_quantile_hats"] = res.logits.detach()[rows, act, :].numpy().copy()
+            seen[-1]["sa_quantiles"] = res.quantiles_tau.detach()[rows, act, :].numpy().copy()
+            margins.append(_fqf_margin(seen[-1]["sa_quantile_hats"], seen[-1]["sa_quantiles"]))
+        return res
+
+    def rec_process(batch, buffer, indices):
+        batch = process_fn(batch, buffer, indices)
+        seen.append(dict(indices=np.array(indices, copy=True),
+                         returns=batch.returns.detach().numpy().copy()))
+        if hasattr(batch, "weight"):
+            seen[-1]["weight"] = np.asarray(batch.weight).copy()
+        return batch
+
+    def rec_learn(batch, **kw_):
+        res = learn(batch, **kw_)
+        seen[-1]["out_weight"] = batch.weight.detach().numpy().copy()
+        return res
+
+    policy.process_fn, policy.learn, policy.forward = rec_process, rec_learn, rec_forward
+    policy.train()
+    np.random.seed(v["seed"])
+    for u in range(FQF_UPDATES):
+        res = policy.update(v["bs"], buf)
+        q = p + f"u{u}_"
+        for k in ("loss", "loss/quantile", "loss/fraction", "loss/entropy"):
+            out[q + k.replace("/", "_")] = np.array(res[k])
+        for k, a in seen[u].items():
+            out[q + k] = a
+        out.update({q + "param_" + k: t.detach().numpy().copy()
+                    for k, t in net.state_dict().items()})
+        out.update({q + "pparam_" + k: t.detach().numpy().copy()
+                    for k, t in propose.state_dict().items()})
+        if v.get("per"):
+            out[q + "leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+    if v.get("per"):
+        out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+            np.array(buf._min_prio)
+    assert len(gaps) == FQF_UPDATES and len(margins) == FQF_UPDATES, (tag, len(gaps))
+    out[p + "top2_gap"], out[p + "min_margin"] = np.array(min(gaps)), np.array(min(margins))
+    return min(gaps), min(margins)
+
+
+def _fqf_conditioning(tag, v, adds, out):
+    """Adam's first steps are sign-like where a gradient is near zero, so a recording can hold a
+    parameter that no second f32 implementation reproduces to the tests' rtol 1e-5 / atol 1e-6.
+    The reference alone shows it: the variant again from initial parameters that are each one
+    FQF_JITTER_ULPS f32 neighbours apart from the recorded ones, three times over.  Returns the
+    largest deviation of a quantile-network parameter between those runs and the recording as a
+    fraction of that tolerance.  Eight neighbours are about what the reference's op sequence on
+    a GPU was seen to differ from it on a CPU (six times a one-neighbour run); the jitter alone
+    is 0.1 of the tolerance, gen_fqf asserts <= 1/4 and the seeds are chosen for it."""
+    worst = 0.0
+    for jitter in (1, 2, 3):
+        again = {"state_keys": None}
+        _fqf_variant(tag, v, adds, again, jitter=jitter)
+        for k, a in again.items():
+            if k.startswith(tag + "_u") and "_param_" in k:
+                assert np.array_equal(again[k.split("param_")[0] + "indices"],
+                                      out[k.split("param_")[0] + "indices"]), k
+                worst = max(worst,
+                            float((np.abs(a - out[k]) / (1e-6 + 1e-5 * np.abs(out[k]))).max()))
+    return worst
+
+
+def gen_fqf():
+    out = {}
+    adds = _dqn_adds(np.random.default_rng(41))
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    for tag, v in FQF_VARIANTS.items():
+        gap, margin = _fqf_variant(tag, v, adds, out)
+        print(tag, "top-two gap", gap, "min_margin", margin)
+        assert gap >= 1e-6, (tag, gap)
+        assert margin >= 1e-5, (tag, margin)
+        if v["optim"] == "adam":
+            cond = _fqf_conditioning(tag, v, adds, out)
+            print(tag, "conditioning", cond)
+            assert cond <= 1 / 4, (tag, cond)
+            out[tag + "_conditioning"] = np.array(cond)
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=DQN_E, S=DQN_S, D=DQN_D, A=DQN_A, gamma=0.97, net=FQF_NET, updates=FQF_UPDATES,
+        init_seed=FQF_INIT_SEED, fraction_lr=FQF_FRACTION_LR, variants=FQF_VARIANTS)))
+    _save("fqf.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
                              "collector_fused", "collector_wide", "rms_wide",
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
-                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn"]
+                             "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn",
+                             "fqf"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -3110,6 +3295,6 @@ if __name__ == "__main__":
                  offpolicy_trainer=gen_offpolicy_trainer,
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
-                 redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn)
+                 redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf)
     for w in which:
         table[w]()
