@@ -79,6 +79,13 @@ constexpr int WP = 68;         // W2 / W3 rows (4i + k banks: conflict-free A fr
 #ifndef COLLECT_TRACE
 #define COLLECT_TRACE 0
 #endif
+// A/B levers of the prologue (see the comment above row_store4)
+#ifndef COLLECT_PROLOGUE
+#define COLLECT_PROLOGUE 0
+#endif
+#ifndef COLLECT_HOST_FAST
+#define COLLECT_HOST_FAST 1
+#endif
 #if COLLECT_TRACE
 #define TSTAMP(i) \
     if (t == 0) ws.trace[((rng_step & 15) * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memrealtime();
@@ -107,6 +114,30 @@ constexpr int WP = 68;         // W2 / W3 rows (4i + k banks: conflict-free A fr
 //    the add divides by it (same bits as a correctly rounded square root per element);
 //  * this step's stored obs rows leave LDS one column per thread over the 16 rows (no integer
 //    division by D per element).
+// Early env phase and prologue A/B (profiles/collect_early_env_ab.log, phase stamps in
+// profiles/collect_early_env_stamps.log; us per step at 4096 x 376 x 17, two passes per call,
+// the parent 21.8-22.2 in every call) --
+//  * kept: the add's fast-path predicate (add_is_fast) evaluated once on the host instead of
+//    from fourteen argument fields by every wave, eight dependent scalar loads at the head of
+//    the chain (first pending-add load issued 1.2 instead of 2.2 us after the workgroup's
+//    start), with the wait for the layer-1 fragments pinned behind the add: 21.31 / 21.46 vs
+//    21.81 / 21.95.  Without the pin the register allocation changes (199 VGPRs from 241),
+//    the fragments' wait lands at their first MFMA, behind the env phase's stores, and
+//    the step is slower: 23.24 / 23.31 vs 23.22 / 21.92.
+//  * dropped: every box_m of the step hashed at the top of the launch and staged in LDS
+//    (16 x KMAX ints, 149 KB in all), the env phase only streaming them out: 25.3 / 25.2 with
+//    the keys behind one LDS barrier after the key threads, 24.75 / 24.91 with every wave
+//    deriving the 16 keys in its own lanes (v_readlane, no barrier) and the hashes between the
+//    issue of the merge's loads and the merge math; with the rows of a column split between
+//    its thread and the NT - D spare threads on top: 25.8 / 26.2 and 24.84 / 24.88.  The hashes are ~3 us of VALU time per SIMD; the env phase without
+//    them is still 3.0 us (3.4 with them): where they are, they run while the phase's stores
+//    and the obs rows stored just before it drain, and ahead of the merge they are exposed.
+//  * dropped, kept as -DCOLLECT_PROLOGUE=1: all prologue loads in flight at once (the totals
+//    converted behind an asm fence -- the compiler otherwise converts, and so waits, in the
+//    block that loads them, twice in a row -- the counters touched before the other loads
+//    issue, reset rows and obs_offset behind them): the barrier behind the merge 0.4 us
+//    earlier by the stamps, the step 21.85 / 22.10 vs 21.95 / 21.93, and on top of the host
+//    predicate 21.35 / 21.33 vs 21.31 / 21.46: not faster in both passes.
 __device__ __forceinline__ void row_store4(float4* p, float4 x) {
     typedef float f4v __attribute__((ext_vector_type(4)));
     const f4v v = {x.x, x.y, x.z, x.w};
@@ -166,6 +197,7 @@ struct Ws {
     RmsState* st[2];
     int64_t nblk;
     uint64_t* trace;
+    int fast_add;  // add_is_fast() of the launch's arguments, evaluated once on the host
 };
 
 // tsrl_rms_exact_stats's layout: float bm1[D], bv1[D], bm2[D], bv2[D]; int64 n1, nd at byte
@@ -273,6 +305,22 @@ __device__ __forceinline__ double slot_f(const long long* p, int i) {
     return CPL ? reinterpret_cast<const double*>(p)[i] : (double)p[i];
 }
 
+// The pending add takes the prefetched path (A1 / A2 of the kernel): a launch behind a merge
+// whose add has the collector's usual shape.  A function of the kernel arguments alone: the
+// host evaluates it once per launch (Ws::fast_add) -- in the kernel its fourteen argument
+// fields cost every wave eight dependent scalar loads of the argument segment at the head
+// of the launch's latency chain.
+__host__ __device__ inline bool add_is_fast(const tsrl_collect_args& a) {
+    const tsrl_add_args& ad = a.add;
+    const bool xp = a.xpipe != 0, defer = !a.no_moments && !xp;
+    const bool merge = (defer || xp) && a.rms_step > 0;
+    return merge && ad.k > 0 && !ad.ids && (a.dim & 3) == 0 && ad.obs_next_src &&
+           ad.obs_next_dst && ad.norm_mean && ad.reset_mean && ad.reset_src && ad.reset_mask &&
+           !ad.obs_src && !ad.obs_next_src_raw && ad.act_src && ad.act_dst &&
+           (ad.act_row_bytes & 3) == 0 && (int)(ad.act_row_bytes >> 2) <= 32 &&
+           aligned16(ad.obs_next_src) && aligned16(ad.obs_next_dst) && aligned16(ad.reset_src);
+}
+
 // SQC = kpad(dim) / 128: the 128-column groups of an observation row (a compile-time bound, so
 // the layer-1 weight fragments and the prefetched rows take only the registers dim needs).
 // CPL: the action-coupled env (a.act_coef != 0, synth.h coupled_val): the env phase runs
@@ -299,6 +347,8 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
     // xpipe: the spec env's keys of step i + d (E)
     __shared__ RowState xs_rs[R], xs_rr[R];
     __shared__ int xs_nd;
+    // the prologue's loads all in flight at once (see the kernel header, "prologue waits")
+    constexpr bool PRO = COLLECT_PROLOGUE && !LW;
     // deferred obs_rms merge: the statistics after the previous step's step rows (obs_next
     // normalisation) and after its reset rows (reset rows, state)
     __shared__ __attribute__((aligned(16))) float sSnapM[KMAX], sSnapV[KMAX], sFinM[KMAX],
@@ -317,6 +367,16 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
     const int64_t rng_step = a.rng_ctr ? *a.rng_ctr : 0;
     // this step's ring position of the pending add (first load: nothing waits behind it)
     const int64_t urel = a.add.k > 0 ? (a.add.rel_dev ? *a.add.rel_dev : a.add.uniform_rel) : 0;
+    // the episode counters of the key rows, loaded before anything else
+    constexpr int KT0 = NT - R;
+    const int ki = t - KT0;
+    const bool krow = ki >= 0 && ki < nrows;
+    int64_t kj = 0, kt = 0, koff = 0;
+    if (krow) {
+        kj = a.ep_j[r0 + ki];
+        kt = a.ep_t[r0 + ki];
+        koff = a.obs_offset[r0 + ki];
+    }
 #if COLLECT_TRACE
     if (t == 0) {
         unsigned xcc, hwid;
@@ -346,22 +406,7 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
     const int arw = t >> 5, aln = t & 31;
     const int nq = D >> 2;
     const int act_n = (int)(ad.act_row_bytes >> 2);
-    const bool fast = merge && ad.k > 0 && !ad.ids && (D & 3) == 0 && ad.obs_next_src && ad.obs_next_dst &&
-                      ad.norm_mean && ad.reset_mean && ad.reset_src && ad.reset_mask &&
-                      !ad.obs_src && !ad.obs_next_src_raw && ad.act_src && ad.act_dst &&
-                      (ad.act_row_bytes & 3) == 0 && act_n <= 32 &&
-                      aligned16(ad.obs_next_src) && aligned16(ad.obs_next_dst) &&
-                      aligned16(ad.reset_src);
-    // the episode counters of the key rows, loaded before anything else
-    constexpr int KT0 = NT - R;
-    const int ki = t - KT0;
-    const bool krow = ki >= 0 && ki < nrows;
-    int64_t kj = 0, kt = 0, koff = 0;
-    if (krow) {
-        kj = a.ep_j[r0 + ki];
-        kt = a.ep_t[r0 + ki];
-        koff = a.obs_offset[r0 + ki];
-    }
+    const bool fast = COLLECT_HOST_FAST ? ws.fast_add != 0 : add_is_fast(a);
     // xpipe: the spec env's counters of these rows (the R threads before the key threads)
     const int si = t - (KT0 - R);
     const bool sgrp = xp && a.spec_raw && si >= 0 && si < R;
@@ -371,6 +416,10 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
         sj = a.spec_j[r0 + si];
         stt = a.spec_t[r0 + si];
     }
+    // the counters are first touched here, ahead of the other loads' issue (vmcnt retires in
+    // order: a later wait for them would wait for those too); they were issued at the top of
+    // the launch.  Without this the compiler folds kt + 1 into the load's block and waits there.
+    if constexpr (PRO) asm volatile("" : "+v"(kj), "+v"(kt));
     const int64_t ar = r0 + arw;
     const bool arow = fast && arw < nrows;
     float4 axs[AQ], axr[AQ];
@@ -396,6 +445,7 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
     float mm0 = 0.f, mv0 = 0.f;
     long long ms1 = 0, mq1 = 0, ms2 = 0, mq2 = 0;  // raw slot words (int64 or f64 bits)
     double mcount = 0.0, mnd = 0.0, mk = 0.0;
+    long long mndr = 0, mkr = 0;  // raw slot words of the two counts
     float xb1 = 0.f, xv1 = 0.f, xb2 = 0.f, xv2 = 0.f;  // xpipe: the previous step's batch moments
     int64_t xn1 = 0, xnd = 0;
     if (merge && xp) {
@@ -417,8 +467,8 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
         const RmsState* sin = ws.st[par];
         const long long* tp = ws.tot[tprev];
         mcount = sin->count;
-        mnd = slot_f<CPL>(tp, 4 * D);
-        mk = slot_f<CPL>(tp, 4 * D + 1);
+        mndr = tp[4 * D];
+        mkr = tp[4 * D + 1];
         if (t < D) {  // D <= KMAX = NT: one column per thread
             mm0 = sin->mean[t];
             mv0 = sin->var[t];
@@ -429,15 +479,20 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
         }
     }
     TSTAMP2(1)
-    // the reset rows of envs that finished (their flag has arrived with the other loads)
-    if (arow && amask) {
-        const float4* r4 = reinterpret_cast<const float4*>(ad.reset_src + ar * D);
+    // the reset rows of envs that finished (their flag has arrived with the other loads).
+    // PRO: issued just ahead of the merge math, whose wait for the totals is the first wait
+    // for any of these loads.
+    auto load_reset_rows = [&]() {
+        if (arow && amask) {
+            const float4* r4 = reinterpret_cast<const float4*>(ad.reset_src + ar * D);
 #pragma unroll
-        for (int j = 0; j < AQ; ++j) {
-            const int q = aln + 32 * j;
-            axr[j] = r4[q < nq ? q : 0];
+            for (int j = 0; j < AQ; ++j) {
+                const int q = aln + 32 * j;
+                axr[j] = r4[q < nq ? q : 0];
+            }
         }
-    }
+    };
+    if constexpr (!PRO) load_reset_rows();
     TSTAMP2(2)
     if (ki >= 0) {
         // this step's counter keys (env.hip box_step_reset_kernel): every read the env phase
@@ -468,6 +523,10 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
         rr[ki] = sr;
         const uint64_t dm = __ballot(dn);
         if (ki == 0) s_nd = __popcll(dm);
+    }
+    // this step's stored obs row of each env.  PRO: behind the reset rows' issue (it reads
+    // obs_offset, and a wait for it is a wait for every load of the wave)
+    auto publish_rows = [&]() {
         if (krow) {
             // this step's stored obs row of the env (see the store loop after the add); with a
             // pending add, block 0 advances the device cursor concurrently, so the position
@@ -477,7 +536,8 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
                                    : (a.obs_rel_dev ? *a.obs_rel_dev : a.obs_uniform_rel);
             s_row[ki] = a.obs_dst + (koff + uo) * (a.obs_pitch ? a.obs_pitch : D);
         }
-    }
+    };
+    if constexpr (!PRO) publish_rows();
     if (sgrp) {
         // xpipe: the spec env's step (i + d) of these rows; its counters and done flags go to
         // HBM now (nothing else in this launch reads them), its rows in the env phase
@@ -494,6 +554,18 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
         xs_rr[si] = sr;
         const uint64_t dm = __ballot(dn);
         if (si == 0) xs_nd = __popcll(dm);
+    }
+    if constexpr (PRO) {
+        publish_rows();
+        load_reset_rows();
+        // the totals are first touched here: without this the compiler converts them to f64
+        // right behind their loads, and so waits for them there
+        asm volatile("" : "+v"(ms1), "+v"(mq1), "+v"(ms2), "+v"(mq2), "+v"(mndr), "+v"(mkr));
+        asm volatile("" : "+v"(mm0), "+v"(mv0), "+v"(mcount));
+    }
+    if (merge && !xp) {
+        mnd = CPL ? __longlong_as_double(mndr) : (double)mndr;
+        mk = CPL ? __longlong_as_double(mkr) : (double)mkr;
     }
     double xcnt = mcount;  // xpipe: the count after the merge
     if (merge) {
@@ -684,6 +756,9 @@ __global__ __launch_bounds__(NT, 1) void collect_box_step_kernel(tsrl_collect_ar
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft) wall[sq][ft] = wp[(sq * 4 + ft) * 64];
     }
+    // the layer-1 fragments are first touched here, behind the add: left to their first MFMA,
+    // the wait for them would sit behind the env phase and wait for its stores as well
+    if constexpr (COLLECT_HOST_FAST && !LW) asm volatile("" : "+v"(wall[SQC - 1][3].w));
     TSTAMP(1)
     // zero padding: columns [D, Kp) and rows past the last env of a partial tile
     for (int i = t; i < (Kp - D) * R; i += NT) sX[(D + i / R) * XP + (i % R)] = 0.0f;
@@ -1076,6 +1151,7 @@ Ws make_ws(const tsrl_collect_args* a) {
     for (int i = 0; i < 2; ++i)
         ws.st[i] = reinterpret_cast<RmsState*>(base + TICKET_BYTES + 3 * TOT_BYTES + i * ST_BYTES);
     ws.trace = reinterpret_cast<uint64_t*>(base + TICKET_BYTES + 3 * TOT_BYTES + 2 * ST_BYTES);
+    ws.fast_add = 0;
     return ws;
 }
 
@@ -1161,7 +1237,8 @@ extern "C" int tsrl_collect_box_step(const tsrl_collect_args* a, void* stream) {
     // data-parallel caller also checks world * k); the coupled env's f64 slot has no such bound
     TSRL_CHECK_ARG(a->act_coef != 0.0f || k <= (int64_t)1 << 17,
                    "tsrl_collect_box_step: k <= 2^17 (exact int64 moments)");
-    const Ws ws = make_ws(a);
+    Ws ws = make_ws(a);
+    ws.fast_add = add_is_fast(*a);
     tsrl_collect_args p = *a;
     p.act_seed = sm64(a->act_seed);
     p.env_seed = sm64(a->env_seed);
