@@ -1203,6 +1203,42 @@ int tsrl_redq_actor_loss_fwd_bwd(const float* q, const float* log_prob, const fl
                                  int64_t b, float* gq, float* g_logp, double* partials,
                                  float* loss, float* g_log_alpha, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * BranchingDQNPolicy / BranchingNet (tianshou/policy/modelfree/bdq.py, utils/net/common.py:
+ * 435-544), csrc/bdq.hip.  Q tables are row-major [b, K, A] f32 (K branches of A actions), any
+ * K >= 1 and A >= 1 (no width limit: nothing is staged per row); b == 0 launches nothing.
+ * tsrl_bdq_combine_fwd: common.py:537-543.  out[r][k][a] = (float)(v[r] + (s[r][k][a] - mean_a'
+ *   s[r][k][a'])) in f64, rounded once (A == 1: out == v exactly).  act_out (NULL: not
+ *   computed) [b, K] = the first-index argmax over a of the ROUNDED out values, a NaN beating
+ *   every number: what out.max(-1)[1] gives on the written tensor.
+ * tsrl_bdq_combine_bwd: g_s[r][k][a] = g_out[r][k][a] - (sum_a' g_out[r][k][a']) / A and
+ *   g_v[r] = sum_k sum_a g_out[r][k][a], f64 sums in a fixed order (lanes by butterfly, a wave's
+ *   branches in index order, the four waves in wave order): bit-identical between runs.
+ * tsrl_bdq_target: bdq.py:50-84.  Per branch a* = argmax_a q_sel[r][k][.] (is_double) or
+ *   argmax_a q_eval[r][k][.] (q_sel unread, may be NULL), first index and NaN first as above;
+ *   m = mean_k q_eval[r][k][a*]; out[r] = (float)(rew[r] + gamma * m * (1 - end[r])), f64.
+ *   end: uint8, done | unfinished (BDQ's end flag, not n-step's terminated).  A NaN m on an
+ *   ended row stays NaN (NaN * 0), as in the reference.
+ * tsrl_bdq_td_fwd_bwd: bdq.py:113-126.  td[r][k] = returns[r] - q[r][k][act[r][k]] (f32, as
+ *   tsrl_dqn_td_fwd_bwd); prio[r] = sum_k td[r][k] (f64, index order, rounded once);
+ *   *loss = mean_r(fl((float)(mean_k td^2) * weight[r])) (weight NULL: 1), the batch sum f64 in
+ *   tsrl_dqn_td_fwd_bwd's fixed order; grad_q [b, K, A] written in full: fl(-2 td weight *
+ *   (1 / (b K))) at the taken action, +0 elsewhere.  An action outside [0, A) in any branch
+ *   gives that row a NaN prio, a NaN loss and an all-zero gradient row.  With K == 1 every
+ *   output equals tsrl_dqn_td_fwd_bwd's at huber = 0 bit for bit.  partials:
+ *   tsrl_dqn_num_partials(b) doubles, read and written only when that is > 1.
+ * ------------------------------------------------------------------------------- */
+int tsrl_bdq_combine_fwd(const float* s, const float* v, int64_t b, int64_t K, int64_t A,
+                         float* out, int64_t* act_out, void* stream);
+int tsrl_bdq_combine_bwd(const float* g_out, int64_t b, int64_t K, int64_t A, float* g_s,
+                         float* g_v, void* stream);
+int tsrl_bdq_target(const float* q_sel, const float* q_eval, const double* rew,
+                    const uint8_t* end, double gamma, int is_double, int64_t b, int64_t K,
+                    int64_t A, float* out, void* stream);
+int tsrl_bdq_td_fwd_bwd(const float* q, const int64_t* act, const float* returns,
+                        const float* weight, int64_t b, int64_t K, int64_t A, float* grad_q,
+                        float* prio, double* partials, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

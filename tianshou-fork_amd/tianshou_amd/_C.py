@@ -273,6 +273,12 @@ _SIGS = {
     "tsrl_redq_q_loss_fwd_bwd": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_redq_actor_loss_fwd_bwd": ([_p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p, _p],
                                      ctypes.c_int),
+    "tsrl_bdq_combine_fwd": ([_p, _p, _i64, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_bdq_combine_bwd": ([_p, _i64, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_bdq_target": ([_p, _p, _p, _p, _d, ctypes.c_int, _i64, _i64, _i64, _p, _p],
+                        ctypes.c_int),
+    "tsrl_bdq_td_fwd_bwd": ([_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+                            ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:

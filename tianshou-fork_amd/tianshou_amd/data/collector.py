@@ -272,6 +272,8 @@ class Collector:
             act_space = act_space[0]
         if hasattr(act_space, "n"):
             return (), torch.int64
+        if hasattr(act_space, "nvec"):  # MultiDiscrete: one index per action dimension
+            return tuple(act_space.shape), torch.int64
         return tuple(act_space.shape), torch.float32
 
     def _fused_step_ok(self, n_step, kk) -> bool:

@@ -1,8 +1,9 @@
 from tianshou_amd.env.cartpole import CartPoleEnv, CartPoleVectorEnv
-from tianshou_amd.env.spaces import Box, Discrete
+from tianshou_amd.env.spaces import Box, Discrete, MultiDiscrete
 from tianshou_amd.env.synthetic import DeviceVectorEnv, SyntheticVectorEnv
 from tianshou_amd.env.venvs import DummyVectorEnv
-from tianshou_amd.env.wrappers import VectorEnvNormObs
+from tianshou_amd.env.wrappers import ContinuousToDiscrete, VectorEnvNormObs
 
-__all__ = ["Box", "CartPoleEnv", "CartPoleVectorEnv", "Discrete", "DeviceVectorEnv",
-           "DummyVectorEnv", "SyntheticVectorEnv", "VectorEnvNormObs"]
+__all__ = ["Box", "CartPoleEnv", "CartPoleVectorEnv", "ContinuousToDiscrete", "Discrete",
+           "DeviceVectorEnv", "DummyVectorEnv", "MultiDiscrete", "SyntheticVectorEnv",
+           "VectorEnvNormObs"]

@@ -37,3 +37,23 @@ class Discrete:
 
     def __repr__(self):
         return f"Discrete({self.n})"
+
+
+class MultiDiscrete:
+    """One Discrete(nvec[i]) per action dimension: int64 vectors of shape (len(nvec),)."""
+
+    def __init__(self, nvec, seed=None):
+        self.nvec = np.asarray(nvec, np.int64)
+        assert self.nvec.ndim == 1 and (self.nvec > 0).all(), "nvec: a vector of positive sizes"
+        self.shape, self.dtype = (len(self.nvec),), np.dtype(np.int64)
+        self.np_random = np.random.default_rng(seed)
+
+    def seed(self, seed=None):
+        self.np_random = np.random.default_rng(seed)
+        return [seed]
+
+    def sample(self):
+        return self.np_random.integers(0, self.nvec).astype(self.dtype)
+
+    def __repr__(self):
+        return f"MultiDiscrete({self.nvec.tolist()})"

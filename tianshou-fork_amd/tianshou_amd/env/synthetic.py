@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from tianshou_amd import _C
-from tianshou_amd.env.spaces import Box, Discrete
+from tianshou_amd.env.spaces import Box, Discrete, MultiDiscrete
 
 
 class DeviceVectorEnv:
@@ -51,7 +51,7 @@ class SyntheticVectorEnv(DeviceVectorEnv):
 
     def __init__(self, num_envs: int, obs_shape, act_dim: int = 1, ep_len: int = 1000,
                  seed: int = 0, device=None, obs_dtype=np.float32, discrete: bool = False,
-                 frame_stack: int = 1, act_coef: float = 0.0):
+                 frame_stack: int = 1, act_coef: float = 0.0, nvec=None):
         """``frame_stack`` S > 1 (u8 only): obs_shape = (S, *frame) holds the last S frames
         like gymnasium's FrameStack wrapper (the Atari setup of
         examples/atari/atari_wrapper.py), so a save_only_last_obs buffer rebuilds it.
@@ -59,7 +59,9 @@ class SyntheticVectorEnv(DeviceVectorEnv):
         MuJoCo env does -- a step's observation is f32(box + f32(c * a[d mod act_dim])) of
         the remapped action a (csrc/synth.h coupled_val).  Its observations are then not
         2^-23-quantised and its transition depends on the action, so the fused collect step
-        runs the env after the actor and sums obs_rms moments in f64."""
+        runs the env after the actor and sums obs_rms moments in f64.
+        ``nvec``: advertise MultiDiscrete(nvec) actions (ignored by the env, so only with
+        ``act_coef == 0``; env/wrappers.py ContinuousToDiscrete couples indices to a Box env)."""
         self.env_num = int(num_envs)
         self.obs_shape = tuple(np.atleast_1d(obs_shape).tolist())
         self.obs_numel = int(np.prod(self.obs_shape))
@@ -83,6 +85,10 @@ class SyntheticVectorEnv(DeviceVectorEnv):
         self.act_dim = int(act_dim)
         assert self.act_coef == 0.0 or (not self.u8 and not discrete), \
             "act_coef needs Box observations and Box actions"
+        if nvec is not None:
+            assert self.act_coef == 0.0 and not discrete, \
+                "nvec (MultiDiscrete actions, ignored) needs act_coef == 0 and discrete=False"
+            self.action_space = MultiDiscrete(nvec)
 
     def _act_arg(self, action, k: int):
         """(pointer, act_dim) of the f32 [k, act_dim] action rows the coupled env reads."""

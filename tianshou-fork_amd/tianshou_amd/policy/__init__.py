@@ -10,6 +10,7 @@ from tianshou_amd.policy.qrdqn import QRDQNPolicy
 from tianshou_amd.policy.rainbow import RainbowPolicy
 from tianshou_amd.policy.iqn import IQNPolicy
 from tianshou_amd.policy.fqf import FQFPolicy
+from tianshou_amd.policy.bdq import BranchingDQNPolicy
 from tianshou_amd.policy.ddpg import DDPGPolicy
 from tianshou_amd.policy.td3 import TD3Policy
 from tianshou_amd.policy.sac import SACPolicy
@@ -18,4 +19,5 @@ from tianshou_amd.policy.redq import REDQPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
            "DQNPolicy", "C51Policy", "QRDQNPolicy", "RainbowPolicy", "IQNPolicy", "FQFPolicy",
-           "DDPGPolicy", "TD3Policy", "SACPolicy", "DiscreteSACPolicy", "REDQPolicy"]
+           "BranchingDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy", "DiscreteSACPolicy",
+           "REDQPolicy"]

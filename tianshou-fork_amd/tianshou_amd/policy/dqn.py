@@ -23,7 +23,8 @@ the hooks below (``_greedy_act``, ``_learn_inputs``, ``_returns_rows``, ``_loss_
 the graph replay as they are; RainbowPolicy (policy/rainbow.py) is C51Policy over NoisyLinear
 layers, IQNPolicy (policy/iqn.py) QRDQNPolicy over ImplicitQuantileNetwork, and FQFPolicy
 (policy/fqf.py) adds a second network with a flat optimiser of its own (``_flats``,
-``_loss_out``, ``_learn_result``).
+``_loss_out``, ``_learn_result``).  BranchingDQNPolicy (policy/bdq.py) has [b, K] actions
+(``_learn_act``) and a target and a loss of its own.
 """
 from copy import deepcopy
 from typing import Any, Dict, Optional, Union
@@ -297,7 +298,7 @@ class DQNPolicy(BasePolicy):
         else:
             dev = next(self.model.parameters()).device
             n = len(batch.returns)
-            act = torch.as_tensor(batch.act, device=dev).reshape(n).to(torch.int64).contiguous()
+            act = self._learn_act(batch, dev, n)
             returns = self._returns_rows(batch, dev, n)
             w = self._loss_weight(weight, dev, n)
             extra = self._learn_inputs(batch)
@@ -340,6 +341,10 @@ class DQNPolicy(BasePolicy):
         """The inputs of one update beyond obs / act / returns / weight (static inputs of the
         learn graph, handed on to ``_before_forward``)."""
         return ()
+
+    def _learn_act(self, batch: Batch, dev, n: int) -> torch.Tensor:
+        """The taken actions as a device int64 [n] (BranchingDQNPolicy: [n, K])."""
+        return torch.as_tensor(batch.act, device=dev).reshape(n).to(torch.int64).contiguous()
 
     def _returns_rows(self, batch: Batch, dev, n: int) -> torch.Tensor:
         return f32_rows(batch.returns, dev, n)

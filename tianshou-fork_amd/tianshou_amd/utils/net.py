@@ -522,6 +522,105 @@ class Net(nn.Module):
         return logits
 
 
+class _BDQCombineFn(torch.autograd.Function):
+    """out = v + s - s.mean(2, keepdim) for s [b, K, A] and v [b] as tsrl_bdq_combine_fwd /
+    tsrl_bdq_combine_bwd; with ``want_act`` the second output is the per-branch greedy action
+    [b, K] of the rounded out values (None otherwise)."""
+
+    @staticmethod
+    def forward(ctx, s, v, want_act):
+        sc, vc = s.detach().float().contiguous(), v.detach().float().contiguous()
+        b, K, A = sc.shape
+        out = torch.empty_like(sc)
+        act = torch.empty(b, K, dtype=torch.int64, device=sc.device) if want_act else None
+        _C.check(_C.lib().tsrl_bdq_combine_fwd(_C.ptr(sc), _C.ptr(vc), b, K, A, _C.ptr(out),
+                                               _C.ptr(act), _C.stream_ptr(sc.device)),
+                 "tsrl_bdq_combine_fwd")
+        ctx.v_shape = v.shape
+        if act is not None:
+            ctx.mark_non_differentiable(act)
+        return out, act
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, _g_act):
+        g = g_out.float().contiguous()
+        b, K, A = g.shape
+        g_s = torch.empty_like(g)
+        g_v = torch.empty(b, dtype=torch.float32, device=g.device)
+        _C.check(_C.lib().tsrl_bdq_combine_bwd(_C.ptr(g), b, K, A, _C.ptr(g_s), _C.ptr(g_v),
+                                               _C.stream_ptr(g.device)), "tsrl_bdq_combine_bwd")
+        return g_s, g_v.view(ctx.v_shape), None
+
+
+class BranchingNet(nn.Module):
+    """Branching dueling Q-network (common.py:435-544, arXiv:1711.08946): a shared trunk
+    ``common``, a state-value head ``value`` and one advantage head per action dimension in
+    ``branches``, built in the reference's order (a seeded construction is bit-equal and a
+    reference ``state_dict`` loads with ``strict=True``).  ``forward`` returns logits
+    [b, K, A] = value + advantage - mean of the advantages inside the branch.
+
+    ``norm_args`` / ``act_args`` sit at the reference's positions, but this package's MLP
+    takes neither: anything but ``None`` raises ``NotImplementedError`` naming the argument.
+
+    On the GPU the aggregation is one tsrl_bdq_combine_fwd launch (one tsrl_bdq_combine_bwd
+    in the backward); without gradients the same launch also writes the greedy action of
+    every branch, which BranchingDQNPolicy.forward picks up (``greedy_act``).  The torch lines
+    (common.py:537-543) run on the CPU, with ``fused_combine = False`` and for non-f32
+    outputs."""
+
+    fused_combine = True
+
+    def __init__(self, state_shape, num_branches: int = 0, action_per_branch: int = 2,
+                 common_hidden_sizes=None, value_hidden_sizes=None, action_hidden_sizes=None,
+                 norm_layer=None, norm_args=None, activation=nn.ReLU, act_args=None,
+                 device="cpu") -> None:
+        super().__init__()
+        if norm_args is not None:
+            raise NotImplementedError("BranchingNet: norm_args is not supported (MLP builds "
+                                      "norm_layer(output_size))")
+        if act_args is not None:
+            raise NotImplementedError("BranchingNet: act_args is not supported (MLP builds "
+                                      "activation())")
+        common_hidden_sizes = common_hidden_sizes or []
+        value_hidden_sizes = value_hidden_sizes or []
+        action_hidden_sizes = action_hidden_sizes or []
+        self.device = device
+        self.num_branches = num_branches
+        self.action_per_branch = action_per_branch
+        self.common = MLP(int(np.prod(state_shape)), 0, common_hidden_sizes, norm_layer,
+                          activation, device)
+        self.value = MLP(common_hidden_sizes[-1], 1, value_hidden_sizes, norm_layer, activation,
+                         device)
+        self.branches = nn.ModuleList([
+            MLP(common_hidden_sizes[-1], action_per_branch, action_hidden_sizes, norm_layer,
+                activation, device) for _ in range(self.num_branches)])
+        self._greedy = None  # (logits, act) of the last no-grad fused forward
+
+    def greedy_act(self, logits: torch.Tensor) -> Optional[torch.Tensor]:
+        """The [b, K] greedy actions the combine launch wrote beside ``logits`` (None when
+        ``logits`` is not the last no-grad fused forward's output)."""
+        g = self._greedy
+        return g[1] if g is not None and g[0] is logits else None
+
+    def forward(self, obs, state: Any = None, **kwargs):
+        common_out = self.common(obs)
+        value_out = self.value(common_out)
+        action_scores = torch.stack([b(common_out) for b in self.branches], 1)
+        self._greedy = None
+        if self.fused_combine and action_scores.is_cuda and action_scores.shape[0] > 0 and \
+                action_scores.dtype == torch.float32 and value_out.dtype == torch.float32:
+            want_act = not (torch.is_grad_enabled() and
+                            (action_scores.requires_grad or value_out.requires_grad))
+            logits, act = _BDQCombineFn.apply(action_scores, value_out.reshape(-1), want_act)
+            if want_act:
+                self._greedy = (logits, act)
+            return logits, state
+        value_out = torch.unsqueeze(value_out, 1)
+        action_scores = action_scores - torch.mean(action_scores, 2, keepdim=True)
+        return value_out + action_scores, state
+
+
 def _module_device(m: nn.Module):
     try:
         return next(m.parameters()).device

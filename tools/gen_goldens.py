@@ -3277,6 +3277,269 @@ def gen_fqf():
     _save("fqf.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 32. BranchingDQNPolicy (tianshou/policy/modelfree/bdq.py) with BranchingNet
+#     (utils/net/common.py:435-544) and ContinuousToDiscrete (env/gym_wrappers.py:8-34):
+#     (a) exploration_noise on seeded NumPy streams; (b) six update() calls per variant over a
+#     _dqn_adds-style stream with [k, K] integer actions; (c) the wrapper's action() outputs;
+#     (d) one seeded collect of the action-coupled synthetic env through the wrapper.
+#     Asserted on the reference's own run, per variant of (b): a sampled row that is truncated
+#     but not terminated, one that is an unfinished last row and one that is terminated (a port
+#     with DQN's end semantics misses the first two); every per-branch relative top-two gap of
+#     the selecting network >= 1e-4; every |sum_k td| >= 1e-2 (the outgoing weights are compared
+#     at rtol 1e-4 with no absolute part).  The sampling seed of a variant is the first from
+#     BDQ_FIRST_SEED on that holds all three; seeds and achieved margins go into the file.
+#     Adam's eps: the reference's op sequence is run a second time with the batch rows reversed
+#     ahead of learn(); if that misses the recorded parameters at rtol 1e-5 / atol 1e-6 under
+#     torch's default eps, every Adam variant is recorded with DSAC_ADAM_EPS (see gen_dsac).
+# --------------------------------------------------------------------------------------
+BDQ_NET = dict(common=[16, 16], value=[8], action=[8])
+BDQ_VARIANTS = {
+    "double_target": dict(K=3, A=5, is_double=True, freq=2, bs=32, optim="adam"),
+    "nature": dict(K=3, A=5, is_double=False, freq=3, bs=65, optim="adam"),
+    "notarget": dict(K=3, A=5, is_double=True, freq=0, bs=64, optim="adam"),
+    "per": dict(K=3, A=5, is_double=True, freq=2, bs=64, optim="adam", per=True),
+    "rms": dict(K=3, A=5, is_double=True, freq=3, bs=64, optim="rms"),
+    "one_branch": dict(K=1, A=6, is_double=True, freq=2, bs=32, optim="adam"),
+}
+BDQ_INIT_SEED, BDQ_FIRST_SEED, BDQ_UPDATES = 11, 8, 6
+BDQ_MIN_GAP, BDQ_MIN_TD = 1e-4, 1e-2
+
+
+def _bdq_adds(rng, K, A):
+    """_dqn_adds' stream with [k, K] integer actions in [0, A), drawn from a generator of
+    their own: every (K, A) sees the same observations, rewards and episode ends."""
+    E, D = DQN_E, DQN_D
+    adds, act_rng = [], np.random.default_rng(42)
+    for t in range(34 + 12):
+        ids = np.arange(E) if t < 34 else np.array([2])
+        k = len(ids)
+        done = rng.random(k) < 0.08
+        term = done & (rng.random(k) < 0.5)
+        adds.append(dict(ids=ids, obs=rng.standard_normal((k, D)).astype(np.float32),
+                         act=act_rng.integers(0, A, (k, K)).astype(np.int64),
+                         rew=rng.standard_normal(k), terminated=term, truncated=done & ~term,
+                         obs_next=rng.standard_normal((k, D)).astype(np.float32)))
+    return adds
+
+
+def _bdq_run(v, adds, seed, adam_eps, reverse=False):
+    """Six reference update() calls of one variant; returns (rows, buffer, net, checks)."""
+    from tianshou.data import PrioritizedVectorReplayBuffer
+    from tianshou.policy import BranchingDQNPolicy
+    from tianshou.utils.net.common import BranchingNet
+    E, S, D, K, A = DQN_E, DQN_S, DQN_D, v["K"], v["A"]
+    if v.get("per"):
+        buf = PrioritizedVectorReplayBuffer(E * S, E, alpha=0.6, beta=0.4)
+    else:
+        buf = VectorReplayBuffer(E * S, E)
+    for a in adds:
+        buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}),
+                buffer_ids=a["ids"])
+    torch.manual_seed(BDQ_INIT_SEED)
+    net = BranchingNet(D, K, A, BDQ_NET["common"], BDQ_NET["value"], BDQ_NET["action"])
+    init = {k: t.detach().numpy().copy() for k, t in net.state_dict().items()}
+    if v["optim"] == "rms":
+        optim = torch.optim.RMSprop(net.parameters(), lr=7e-4, eps=1e-5, alpha=0.99)
+    else:
+        optim = torch.optim.Adam(net.parameters(), lr=1e-3, eps=adam_eps)
+    policy = BranchingDQNPolicy(net, optim, discount_factor=0.97, estimation_step=1,
+                                target_update_freq=v["freq"], is_double=v["is_double"])
+    process_fn, learn, forward = policy.process_fn, policy.learn, policy.forward
+    seen = []
+    chk = dict(gap=np.inf, min_td=np.inf, trunc=0, unfinished=0, term=0)
+    selecting = "model" if v["is_double"] or v["freq"] == 0 else "model_old"
+
+    def rec_forward(batch, state=None, model="model", input="obs", **kw):
+        res = forward(batch, state, model=model, input=input, **kw)
+        if input == "obs_next" and model == selecting:
+            chk["gap"] = min(chk["gap"], _top2_gap(res.logits.detach().numpy().reshape(-1, A)))
+        return res
+
+    def rec_process(batch, buffer, indices):
+        batch = process_fn(batch, buffer, indices)
+        ret = batch.returns.detach().numpy()
+        assert ret.shape == (len(indices), K, A) and (ret == ret[:, :1, :1]).all()
+        seen.append(dict(indices=np.array(indices, copy=True), returns=ret[:, 0, 0].copy()))
+        if hasattr(batch, "weight"):
+            seen[-1]["weight"] = batch.weight.detach().numpy().copy()
+        term, trunc = buffer.terminated[indices], buffer.truncated[indices]
+        chk["term"] += int(term.sum())
+        chk["trunc"] += int((trunc & ~term).sum())
+        chk["unfinished"] += int(np.isin(indices, buffer.unfinished_index()).sum())
+        return batch[np.arange(len(indices))[::-1].copy()] if reverse else batch
+
+    def rec_learn(batch, **kw):
+        res = learn(batch, **kw)
+        td = batch.weight.detach().numpy().copy()
+        seen[-1]["td_error"] = td[::-1].copy() if reverse else td
+        chk["min_td"] = min(chk["min_td"], float(np.abs(td).min()))
+        if reverse:  # post_process_fn pairs the weights with the unreversed indices
+            batch.weight = batch.weight.flip(0)
+        return res
+
+    policy.forward, policy.process_fn, policy.learn = rec_forward, rec_process, rec_learn
+    np.random.seed(seed)
+    for u in range(BDQ_UPDATES):
+        res = policy.update(v["bs"], buf)
+        row = seen[u]
+        row["loss"] = np.array(res["loss"])
+        row["params"] = np.concatenate([t.detach().numpy().ravel() for t in net.parameters()])
+        if v["freq"] > 0:
+            row["params_old"] = np.concatenate([t.detach().numpy().ravel()
+                                                for t in policy.model_old.parameters()])
+        if v.get("per"):
+            row["leaves"] = np.asarray(buf.weight[np.arange(buf.maxsize)]).copy()
+    return seen, buf, init, chk
+
+
+def _bdq_holds(chk):
+    return chk["gap"] >= BDQ_MIN_GAP and chk["min_td"] >= BDQ_MIN_TD and chk["trunc"] > 0 and \
+        chk["unfinished"] > 0 and chk["term"] > 0
+
+
+def _bdq_variants(adam_eps):
+    """Every variant of (b) at Adam eps ``adam_eps``: (arrays, per-variant checks, worst
+    deviation of the rows-reversed rerun of an Adam variant from the recorded parameters in
+    units of the bound rtol 1e-5 / atol 1e-6)."""
+    out, checks, worst = {}, {}, 0.0
+    for tag, v in BDQ_VARIANTS.items():
+        adds = _bdq_adds(np.random.default_rng(41), v["K"], v["A"])
+        for seed in range(BDQ_FIRST_SEED, BDQ_FIRST_SEED + 2000):
+            seen, buf, init, chk = _bdq_run(v, adds, seed, adam_eps)
+            if _bdq_holds(chk):
+                break
+        else:
+            raise AssertionError(f"{tag}: no sampling seed holds the recording's conditions")
+        assert _bdq_holds(chk), (tag, chk)
+        checks[tag] = dict(seed=seed, **chk)
+        print(tag, checks[tag])
+        p = tag + "_"
+        out.update({p + "init_" + k: a for k, a in init.items()})
+        for k in seen[0]:
+            out[p + k] = np.stack([row[k] for row in seen])
+        out[p + "add_act"] = np.concatenate([a["act"] for a in adds])
+        if v.get("per"):
+            out[p + "max_prio"], out[p + "min_prio"] = np.array(buf._max_prio), \
+                np.array(buf._min_prio)
+        if v["optim"] == "adam":
+            rev = _bdq_run(v, adds, seed, adam_eps, reverse=True)[0]
+            for a, b in zip(seen, rev):
+                np.testing.assert_array_equal(a["indices"], b["indices"])
+                dev = np.abs(a["params"] - b["params"]) / (1e-6 + 1e-5 * np.abs(a["params"]))
+                worst = max(worst, float(dev.max()))
+    return out, checks, worst
+
+
+def gen_bdq():
+    from tianshou.env import ContinuousToDiscrete
+    from tianshou.policy import BranchingDQNPolicy
+    from tianshou.utils.net.common import BranchingNet
+    out = {}
+    # (a) exploration_noise
+    cases = []
+    for bsz in (1, 65, 257):
+        for K in (1, 4):
+            for A in (2, 25):
+                for eps in (0.3, 1.0):
+                    rng = np.random.default_rng(100 + len(cases))
+                    net = BranchingNet(3, K, A, [4], [4], [4])
+                    policy = BranchingDQNPolicy(net, None)
+                    policy.set_eps(eps)
+                    act = rng.integers(0, A, (bsz, K)).astype(np.int64)
+                    batch = Batch(obs=np.zeros((bsz, 3), np.float32))
+                    seed = 700 + len(cases)
+                    p = f"noise{len(cases)}_"
+                    out[p + "act_in"] = act.copy()
+                    np.random.seed(seed)
+                    out[p + "act_out"] = policy.exploration_noise(act, batch).copy()
+                    st = np.random.get_state()
+                    out[p + "state_keys"], out[p + "state_pos"] = st[1].copy(), np.array(st[2])
+                    cases.append(dict(bsz=bsz, K=K, A=A, eps=eps, seed=seed))
+    out["noise_cfg"] = np.array(json.dumps(cases))
+
+    # (b) update variants
+    adds = _bdq_adds(np.random.default_rng(41), 3, 5)
+    out["add_len"] = np.array([len(a["ids"]) for a in adds])
+    for k in adds[0]:
+        if k != "act":  # per variant (its K and A): <tag>_add_act
+            out["add_" + k] = np.concatenate([a[k] for a in adds])
+    adam_eps = 1e-8  # torch's default
+    arrays, checks, worst = _bdq_variants(adam_eps)
+    print("rows-reversed rerun, default Adam eps: worst deviation / bound", worst)
+    reversed_default = worst
+    if worst > 1.0:
+        adam_eps = DSAC_ADAM_EPS
+        arrays, checks, worst = _bdq_variants(adam_eps)
+        print("rows-reversed rerun, Adam eps", adam_eps, ": worst deviation / bound", worst)
+        assert worst <= 1.0, worst
+    out.update(arrays)
+    out["learn_cfg"] = np.array(json.dumps(dict(
+        E=DQN_E, S=DQN_S, D=DQN_D, gamma=0.97, net=BDQ_NET, updates=BDQ_UPDATES,
+        init_seed=BDQ_INIT_SEED, adam_eps=adam_eps, reversed_default_eps=reversed_default,
+        reversed=worst, min_gap=BDQ_MIN_GAP, min_td=BDQ_MIN_TD, variants=BDQ_VARIANTS,
+        checks=checks)))
+
+    # (c) the wrapper's action()
+    low, high = np.array([-2.0, -0.5], np.float32), np.array([1.0, 3.0], np.float32)
+
+    class BoxEnv(gym.Env):
+        action_space = gym.spaces.Box(low, high, (2,), np.float32)
+
+    rng = np.random.default_rng(5)
+    wraps = []
+    for i, apd in enumerate((5, [3, 6])):
+        w = ContinuousToDiscrete(BoxEnv(), apd)
+        nvec = np.asarray(w.action_space.nvec)
+        act2 = rng.integers(0, nvec, (7, 2)).astype(np.int64)
+        p = f"wrap{i}_"
+        for d in range(2):
+            out[p + f"mesh{d}"] = np.asarray(w.mesh[d], np.float64)
+        out[p + "act1"], out[p + "out1"] = act2[0].copy(), np.asarray(w.action(act2[0]))
+        out[p + "act2"], out[p + "out2"] = act2, np.asarray(w.action(act2))
+        wraps.append(dict(action_per_dim=apd, nvec=nvec.tolist()))
+    out["wrap_cfg"] = np.array(json.dumps(dict(low=low.tolist(), high=high.tolist(),
+                                               cases=wraps)))
+
+    # (d) one collect with exploration noise through the wrapper
+    n_env, n_step, Dc, Ac, L, coef, Ad, eps = 4, 200, 5, 2, 7, 0.05, 5, 0.5
+    CoupledSynthGymEnv = _coupled_env(Dc, Ac, L, coef, low, high)
+    for seed in range(1800, 1900):
+        envs = DummyVectorEnv([lambda e=e: ContinuousToDiscrete(CoupledSynthGymEnv(e), Ad)
+                               for e in range(n_env)])
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        net = BranchingNet(Dc, Ac, Ad, [16, 16], [8], [8])
+        init = {k: t.detach().numpy().copy() for k, t in net.state_dict().items()}
+        policy = BranchingDQNPolicy(net, torch.optim.Adam(net.parameters(), lr=1e-3),
+                                    target_update_freq=10)
+        policy.set_eps(eps)
+        forward, gaps = policy.forward, []
+
+        def rec_forward(batch, state=None, **kw):
+            res = forward(batch, state, **kw)
+            gaps.append(_top2_gap(res.logits.detach().numpy().reshape(-1, Ad)))
+            return res
+
+        policy.forward = rec_forward
+        buf = VectorReplayBuffer(n_env * 60, n_env)
+        c = Collector(policy, envs, buf, exploration_noise=True)
+        res = c.collect(n_step=n_step)
+        if min(gaps) >= BDQ_MIN_GAP:
+            break
+    assert min(gaps) >= BDQ_MIN_GAP, min(gaps)
+    print("collect seed", seed, "min greedy top-two gap", min(gaps))
+    out.update(_stats_arrays("col_", res))
+    out.update(_buf_arrays("col_buf_", buf))
+    assert out["col_buf_act"].dtype == np.int64 and out["col_buf_act"].shape[1] == Ac
+    out.update({"col_init_" + k: a for k, a in init.items()})
+    out.update(_np_state_arrays("col_"))
+    out["col_cfg"] = np.array(json.dumps(dict(
+        seed=seed, E=n_env, n_step=n_step, size=n_env * 60, D=Dc, K=Ac, A=Ad, L=L, env_seed=9,
+        act_coef=coef, eps=eps, low=low.tolist(), high=high.tolist(), min_gap=min(gaps))))
+    _save("bdq.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
@@ -3284,7 +3547,7 @@ if __name__ == "__main__":
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
                              "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn",
-                             "fqf"]
+                             "fqf", "bdq"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -3295,6 +3558,7 @@ if __name__ == "__main__":
                  offpolicy_trainer=gen_offpolicy_trainer,
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
-                 redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf)
+                 redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf,
+                 bdq=gen_bdq)
     for w in which:
         table[w]()

@@ -70,6 +70,15 @@ class Discrete(Space):
         return int(self.np_random.integers(self.n))
 
 
+class MultiDiscrete(Space):
+    def __init__(self, nvec, dtype=np.int64, seed=None):
+        self.nvec = np.asarray(nvec, dtype)
+        super().__init__(self.nvec.shape, np.dtype(dtype), seed)
+
+    def sample(self):
+        return self.np_random.integers(0, self.nvec).astype(self.dtype)
+
+
 class _OtherSpace(Space):
     pass
 
@@ -91,6 +100,22 @@ class Wrapper(Env):
         self.env = env
 
 
+class ActionWrapper(Wrapper):
+    """gymnasium.ActionWrapper: step() hands the env ``self.action(act)``; everything the
+    wrapper does not define itself is the wrapped env's."""
+
+    def __getattr__(self, name):
+        if name == "env":
+            raise AttributeError(name)
+        return getattr(self.env, name)
+
+    def reset(self, **kwargs):
+        return self.env.reset(**kwargs)
+
+    def step(self, action):
+        return self.env.step(self.action(action))
+
+
 class _Graph:
     def __init__(self, *a, **k):
         self.nodes = {}
@@ -106,12 +131,12 @@ def install():
     _module("numba", njit=_njit, _tsrl_stub=True)
     _module("h5py", File=_Inert, Dataset=_Inert, Group=_Inert)
     spaces = _module("gymnasium.spaces", Space=Space, Box=Box, Discrete=Discrete,
-                     MultiDiscrete=_OtherSpace, MultiBinary=_OtherSpace, Dict=_OtherSpace,
+                     MultiDiscrete=MultiDiscrete, MultiBinary=_OtherSpace, Dict=_OtherSpace,
                      Tuple=_OtherSpace)
     spaces.__path__ = []
     _module("gymnasium.spaces.discrete", Discrete=Discrete)
     wrappers = _module("gymnasium.wrappers", TimeLimit=Wrapper)
-    _module("gymnasium", Env=Env, Space=Space, Wrapper=Wrapper, ActionWrapper=Wrapper,
+    _module("gymnasium", Env=Env, Space=Space, Wrapper=Wrapper, ActionWrapper=ActionWrapper,
             spaces=spaces, wrappers=wrappers, __version__="0.29.1")
     _module("pettingzoo", __version__="1.24.0")
     _module("pettingzoo.utils")
