@@ -243,8 +243,9 @@ __device__ Welford block_welford(Welford v, double* sh /*[3*TPB]*/) {
 }
 
 // Block-wide Chan merge with wave shuffles (xor butterfly inside each wave, then the 4 wave
-// results folded in wave order by thread 0): fixed order -> deterministic; result valid in
-// thread 0.  `sh` holds NWAVE entries.
+// results as a pairwise tree ((w0,w1),(w2,w3))): fixed order -> deterministic; result valid in
+// thread 0.  `sh` holds NWAVE entries.  The same tree as block_welford_full, so a full tile
+// gives the same bits through either (tests/test_gpu_gae_edges.py pins this).
 __device__ __forceinline__ Welford block_welford_fast(Welford v, Welford* sh) {
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) {
@@ -257,10 +258,8 @@ __device__ __forceinline__ Welford block_welford_fast(Welford v, Welford* sh) {
     const int w = threadIdx.x / kWave;
     if ((threadIdx.x & (kWave - 1)) == 0) sh[w] = v;
     __syncthreads();
-    Welford r = sh[0];
-#pragma unroll
-    for (int i = 1; i < NWAVE; ++i) r = chan(r, sh[i]);
-    return r;
+    static_assert(NWAVE == 4, "pairwise wave fold assumes 4 waves");
+    return chan(chan(sh[0], sh[1]), chan(sh[2], sh[3]));
 }
 
 // Chan merge of two partials with equal power-of-two counts (every lane of a full tile holds
@@ -793,6 +792,7 @@ extern "C" int tsrl_gae_f64v(const double* v_s, const double* v_s_next, const do
     if (n == 0) return 0;
     TSRL_CHECK_ARG(v_s && v_s_next && rew && terminated && truncated,
                    "tsrl_gae_f64v: null input pointer");
+    TSRL_CHECK_ARG(row_len >= 0, "tsrl_gae_f64v: row_len < 0");
     GaeArgs p = {};
     p.vs64 = v_s;
     p.vn64 = v_s_next;
