@@ -288,11 +288,7 @@ static int clip_step(const char* what, float* param, float* grad, float* m, floa
     // slice per CU of this device (hipDeviceAttributeMultiprocessorCount, 256 on MI355X);
     // larger parameter sets take the separate norm launch
     const int fused_norm = grid <= n_cus();
-    if (max_norm > 0.0f && !fused_norm) {
-        hipLaunchKernelGGL(norm_partials_kernel, dim3((unsigned)grid), dim3(OTPB), 0,
-                           as_stream(stream), grad, n, partials);
-        TSRL_LAUNCH_CHECK(what);
-    }
+    // (every argument check precedes the first launch: a refused call launches nothing)
     const StepArgs a{lr, max_norm};
     SplitOut so{nullptr, 0, 0, 1, 1, 0};
     if (split) {
@@ -302,6 +298,11 @@ static int clip_step(const char* what, float* param, float* grad, float* m, floa
                        "%s: bad first-layer split ranges", what);
         so = SplitOut{reinterpret_cast<__bf16*>(split->out), split->off_a, split->off_c,
                       split->d, split->kp, 128 * split->kp};
+    }
+    if (max_norm > 0.0f && !fused_norm) {
+        hipLaunchKernelGGL(norm_partials_kernel, dim3((unsigned)grid), dim3(OTPB), 0,
+                           as_stream(stream), grad, n, partials);
+        TSRL_LAUNCH_CHECK(what);
     }
     hipLaunchKernelGGL(clip_step_kernel<Rule>, dim3((unsigned)grid), dim3(OTPB), 0,
                        as_stream(stream), param, grad, m, v, n, step, nstep, a, rule, partials,
