@@ -1239,6 +1239,66 @@ int tsrl_bdq_td_fwd_bwd(const float* q, const int64_t* act, const float* returns
                         const float* weight, int64_t b, int64_t K, int64_t A, float* grad_q,
                         float* prio, double* partials, float* loss, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The discrete offline policies (tianshou/policy/imitation/discrete_bcq.py, discrete_cql.py,
+ * discrete_crr.py), csrc/offline.hip.  Tables are row-major [b, A] f32, act int64 [b].  All
+ * per-row arithmetic is f64, rounded once; batch sums are f64 in a fixed order (tsrl_dqn_td_
+ * fwd_bwd's for the [b, A] kernels, tsrl_qr_loss_fwd_bwd's for the CQL kernel): bit-identical
+ * between runs.  Every logsumexp subtracts the row maximum.  An action outside [0, A) gives NaN
+ * losses and no gradient at the taken action.  partials of the [b, A] kernels:
+ * 3 * tsrl_dqn_num_partials(b) doubles, read and written only when that count is > 1.
+ * tsrl_bcq_select: discrete_bcq.py:97-99.  Action a of row r is allowed unless
+ *   fl32(logits[r][a] - max_a' logits[r][a']) < (float)log_tau (torch's f32 test: a NaN ratio is
+ *   allowed, log_tau = -inf allows all).  paper == 0: act[r] = the first allowed action, which
+ *   is what the reference's (q - inf * mask).argmax returns (inf * 0 is NaN on every allowed
+ *   action, and argmax takes the first NaN); q of an unallowed action is not read.  paper != 0:
+ *   the first index of the maximum of q over the allowed actions, a NaN beating every number
+ *   (arXiv:1910.01708 Eq. 17).  With q_eval and val (both or neither): val[r] =
+ *   q_eval[r][act[r]], _target_q's gather (:78-80).  b == 0 launches nothing.
+ * tsrl_bcq_loss_fwd_bwd: discrete_bcq.py:110-118.  loss[0..4) = total, q, i, reg: q = mean_r
+ *   smooth_l1(q[r][act] - returns[r]) (beta 1), i = mean_r (lse(logits[r]) - logits[r][act]),
+ *   reg = the mean of logits^2 over all b A entries, total = q + i + weight_reg * reg.  grad_q
+ *   (zero off the taken action) and grad_logits (dense) are the gradients of total.
+ * tsrl_cql_qr_loss_fwd_bwd: discrete_cql.py:57-76.  curr [b, A, N] contiguous, returns [b, N],
+ *   tau_hat [N], weight [b] or NULL, N <= TSRL_DIST_MAX_N, A <= TSRL_CQL_MAX_ACTIONS.
+ *   loss[0..3) = total, qr, cql: qr and prio [b] as tsrl_qr_loss_fwd_bwd's loss and prio (bit
+ *   for bit); q[r][a] = mean_n curr[r][a][n]; cql = mean_r lse(q[r]) - mean_r q[r][act] (not
+ *   weighted); total = qr + min_q_weight * cql.  grad [b, A, N] is dense: min_q_weight *
+ *   (softmax(q[r])[a] - [a == act]) / (b N) everywhere plus the Huber gradient on the taken
+ *   row; with min_q_weight == 0 it equals tsrl_qr_loss_fwd_bwd's bit for bit.  partials: 3 b
+ *   doubles, always needed.
+ * tsrl_crr_loss_fwd_bwd: discrete_crr.py:88-117.  target = rew + gamma * (done ? 0 : sum_a
+ *   softmax(t_logits)_a t_q_a); critic = mean 0.5 (q_act - target)^2; adv = q_act - sum_a
+ *   softmax(logits)_a q_a; coef = exp(adv / beta) clamped at ratio_upper_bound (mode 0),
+ *   [adv > 0] (mode 1) or 1 (mode 2); actor = mean_r(-(logits_act - lse(logits))) * mean_r(coef)
+ *   -- the reference multiplies log_prob [b] by the coefficient [b, 1], which broadcasts to
+ *   [b, b], so its mean is the product of the two means; cql = mean (lse(q) - q_act).
+ *   loss[0..4) = total, actor, critic, cql with total = actor + critic + min_q_weight * cql.
+ *   Two passes: the terms with their sums, then the gradients.  partials: 2 + 4 *
+ *   tsrl_dqn_num_partials(b) doubles, always needed.  As in the reference the coefficient is not detached: in mode 0, while
+ *   exp(adv / beta) < ratio_upper_bound, the gradients include the path through it; at or above
+ *   the bound (an overflowing exponential included) the coefficient is the bound and that path
+ *   is zero.  done: uint8 [b], rew: f32 [b].
+ * ------------------------------------------------------------------------------- */
+#define TSRL_CQL_MAX_ACTIONS 1024
+int tsrl_bcq_select(const float* q, const float* logits, double log_tau, const float* q_eval,
+                    int paper, int64_t b, int64_t num_actions, int64_t* act, float* val,
+                    void* stream);
+int tsrl_bcq_loss_fwd_bwd(const float* q, const float* logits, const int64_t* act,
+                          const float* returns, double weight_reg, int64_t b,
+                          int64_t num_actions, float* grad_q, float* grad_logits,
+                          double* partials, float* loss, void* stream);
+int tsrl_cql_qr_loss_fwd_bwd(const float* curr, const int64_t* act, const float* returns,
+                             const float* tau_hat, const float* weight, double min_q_weight,
+                             int64_t b, int64_t num_actions, int64_t n, float* grad, float* prio,
+                             double* partials, float* loss, void* stream);
+int tsrl_crr_loss_fwd_bwd(const float* q, const float* logits, const int64_t* act,
+                          const float* t_logits, const float* t_q, const float* rew,
+                          const uint8_t* done, double gamma, int mode, double beta,
+                          double ratio_upper_bound, double min_q_weight, int64_t b,
+                          int64_t num_actions, float* grad_q, float* grad_logits,
+                          double* partials, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@
 #include <float.h>
 
 #include "loss_sum.h"
+#include "qr_pair.h"
 #include "tsrl_common.h"
 
 namespace tsrl {
@@ -210,29 +211,8 @@ __global__ __launch_bounds__(TPB) void qr_loss_kernel(
     const float* c_row = curr + (r * A + a) * N;
     double hub = 0.0, pri = 0.0;
     for (int64_t i = t; i < N; i += blockDim.x) {
-        const double th = (double)c_row[i], tau = (double)tau_hat[i];
-        const double k_neg = fabs(tau - 1.0), k_pos = fabs(tau);  // |tau - 1{u <= 0}|
-        double hi = 0.0, g = 0.0;
-        for (int64_t j = 0; j < N; ++j) {
-            const double u = (double)lds[j] - th;
-            const double au = fabs(u);
-            const double h = au < 1.0 ? 0.5 * u * u : au - 0.5;  // smooth_l1, beta 1
-            const double k = u <= 0.0 ? k_neg : k_pos;
-            hi += h * k;
-            pri += h;
-            g += fmin(fmax(u, -1.0), 1.0) * k;
-        }
-        if (hi != hi) {
-            // Some u_ij is NaN (a NaN target or quantile, inf - inf): h is NaN there, but fmin /
-            // fmax above made the derivative -1.  torch's smooth_l1 backward keeps the NaN, so
-            // this quantile's sum is taken again with it kept.  (hi is also NaN at inf * 0, a
-            // tau_hat of exactly 0 or 1; the second pass then gives what the first one gave.)
-            g = 0.0;
-            for (int64_t j = 0; j < N; ++j) {
-                const double u = (double)lds[j] - th;
-                g += (u != u ? u : fmin(fmax(u, -1.0), 1.0)) * (u <= 0.0 ? k_neg : k_pos);
-            }
-        }
+        double hi, g;
+        qr_pair_walk(lds, N, (double)c_row[i], (double)tau_hat[i], hi, g, pri);
         hub += hi;
         g_row[a * N + i] = (float)(-g * gscale);
     }

@@ -279,6 +279,13 @@ _SIGS = {
                         ctypes.c_int),
     "tsrl_bdq_td_fwd_bwd": ([_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p],
                             ctypes.c_int),
+    "tsrl_bcq_select": ([_p, _p, _d, _p, ctypes.c_int, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_bcq_loss_fwd_bwd": ([_p, _p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p],
+                              ctypes.c_int),
+    "tsrl_cql_qr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _d, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+                                 ctypes.c_int),
+    "tsrl_crr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _p, _p, _d, ctypes.c_int, _d, _d, _d, _i64,
+                               _i64, _p, _p, _p, _p, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
@@ -287,6 +294,7 @@ NOISY_DESC_WORDS = 10
 DUELING_MAX_ROW = 4096        # TSRL_DUELING_MAX_ROW
 ERR_DUELING_ROW = 100001      # TSRL_ERR_DUELING_ROW
 DIST_MAX_N = 4096             # TSRL_DIST_MAX_N: atoms / quantiles the C51 and QR loss kernels take
+CQL_MAX_ACTIONS = 1024        # TSRL_CQL_MAX_ACTIONS: actions tsrl_cql_qr_loss_fwd_bwd stages per row
 IQN_MAX_COSINES = 256         # TSRL_IQN_MAX_COSINES: cosines tsrl_iqn_embed_fwd stages per fraction
 
 EXPORTED = tuple(_SIGS)

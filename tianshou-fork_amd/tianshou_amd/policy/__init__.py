@@ -16,8 +16,11 @@ from tianshou_amd.policy.td3 import TD3Policy
 from tianshou_amd.policy.sac import SACPolicy
 from tianshou_amd.policy.discrete_sac import DiscreteSACPolicy
 from tianshou_amd.policy.redq import REDQPolicy
+from tianshou_amd.policy.discrete_bcq import DiscreteBCQPolicy
+from tianshou_amd.policy.discrete_cql import DiscreteCQLPolicy
+from tianshou_amd.policy.discrete_crr import DiscreteCRRPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
            "DQNPolicy", "C51Policy", "QRDQNPolicy", "RainbowPolicy", "IQNPolicy", "FQFPolicy",
            "BranchingDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy", "DiscreteSACPolicy",
-           "REDQPolicy"]
+           "REDQPolicy", "DiscreteBCQPolicy", "DiscreteCQLPolicy", "DiscreteCRRPolicy"]

@@ -165,7 +165,7 @@ class DQNPolicy(BasePolicy):
             return None
         fa = self._flat
         if fa is None:
-            fa = self._flat = FlatAdam(self.model.parameters())
+            fa = self._flat = FlatAdam(self._flat_params())
         if not fa.bind_adam(self.optim):
             self._old_flat = None
             return None
@@ -173,6 +173,11 @@ class DQNPolicy(BasePolicy):
             self._old_src = fa.flat_param
             self._old_flat = mirror_target(self.model_old, fa.params, self._old_src)
         return fa
+
+    def _flat_params(self):
+        """The parameters the flat storage holds, the Q-network's first and in its order (the
+        target mirror covers that prefix); DiscreteBCQPolicy adds its imitator's."""
+        return self.model.parameters()
 
     def _old_is_flat(self, fa: FlatAdam) -> bool:
         return target_mirrored(self.model_old, self._old_flat, self._old_src, fa.flat_param)

@@ -1,15 +1,18 @@
-"""BaseTrainer, OffpolicyTrainer and OnpolicyTrainer (tianshou/trainer/base.py:22-563): the
-epoch iterator that drives a Collector, a policy and a test Collector.
+"""BaseTrainer, OfflineTrainer, OffpolicyTrainer and OnpolicyTrainer
+(tianshou/trainer/base.py:22-563): the epoch iterator that drives a Collector, a policy and a
+test Collector.
 
 One epoch collects ``step_per_epoch`` environment steps in chunks of ``step_per_collect``
 steps or ``episode_per_collect`` episodes, updates the policy after every chunk and ends
 with a test.  ``OffpolicyTrainer`` makes ``round(update_per_step * n/st)`` calls of
 ``policy.update(batch_size, buffer)`` per chunk -- on the device path each one is a fused
 sample (``VectorReplayBuffer.sample_nstep``) and a graph replay; ``OnpolicyTrainer`` makes one
-``policy.update(0, buffer, batch_size=, repeat=)`` over the whole buffer and resets it.
+``policy.update(0, buffer, batch_size=, repeat=)`` over the whole buffer and resets it;
+``OfflineTrainer`` has no train collector and makes one sampled update from the fixed ``buffer``
+per step of an epoch.
 
 Not built: loggers beyond the no-op default (any object with the reference BaseLogger's
-methods is accepted), ``resume_from_log``, OfflineTrainer and OffpolicyFullBufferTrainer.
+methods is accepted), ``resume_from_log`` and OffpolicyFullBufferTrainer.
 """
 import time
 from abc import ABC, abstractmethod
@@ -295,6 +298,16 @@ class BaseTrainer(ABC):
         self.log_update_data(data, losses)
 
 
+class OfflineTrainer(BaseTrainer):
+    """One sampled update from the fixed ``buffer`` per step (base.py:509-516): an epoch is
+    ``step_per_epoch`` gradient steps, and ``env_step`` counts ``gradient_step * batch_size``."""
+
+    def policy_update_fn(self, data: Dict[str, Any], result: Optional[Dict[str, Any]] = None
+                         ) -> None:
+        assert self.buffer
+        self._sample_and_update(self.buffer, data)
+
+
 class OffpolicyTrainer(BaseTrainer):
     """``round(update_per_step * n/st)`` sampled updates after every collect
     (base.py:519-535)."""
@@ -314,6 +327,11 @@ class OnpolicyTrainer(BaseTrainer):
         assert self.train_collector is not None
         self._update_on_entire_buffer(self.train_collector.buffer, data)
         self.train_collector.reset_buffer(keep_statistics=True)
+
+
+def offline_trainer(*args: Any, **kwargs: Any) -> Dict[str, Union[float, str]]:
+    """``OfflineTrainer(...).run()``."""
+    return OfflineTrainer(*args, **kwargs).run()
 
 
 def offpolicy_trainer(*args: Any, **kwargs: Any) -> Dict[str, Union[float, str]]:

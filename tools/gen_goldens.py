@@ -3540,6 +3540,165 @@ def gen_bdq():
     _save("bdq.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 32. The discrete offline policies (tianshou/policy/imitation/discrete_bcq.py,
+#     discrete_cql.py, discrete_crr.py): five update() calls per variant over gen_dqn's add()
+#     stream, the state_dict (online and target networks) before the first and after every
+#     update, and a forward on fixed observations.  The init seed of every variant is the first
+#     of OFFLINE_INIT_SEEDS on which the reference alone keeps: every BCQ ratio the run
+#     evaluates 1e-3 off log_tau; every greedy top-two gap >= 1e-3 (_top2_gap); every CRR
+#     coefficient 1e-3 relative off ratio_upper_bound and every binary advantage 1e-4 off
+#     zero; and the run with every sampled batch reversed (another f32 summation order)
+#     within a quarter of the parameter bound, 2.5e-7 -- no parameter on one of Adam's
+#     sign-like first steps.  tau, beta and the bound are chosen so that the recorded runs mask
+#     actions and clamp coefficients (the counts are in the file's checks).
+# --------------------------------------------------------------------------------------
+OFFLINE_VARIANTS = {
+    "bcq": dict(kind="bcq", freq=2, n_step=3, bs=32, optim="adam"),
+    "bcq_shared": dict(kind="bcq", shared=True, freq=3, n_step=1, bs=64, optim="adam"),
+    "bcq_rms": dict(kind="bcq", freq=2, n_step=1, bs=64, optim="rms"),
+    "cql": dict(kind="cql", freq=2, n_step=1, bs=32, optim="adam"),
+    "crr_exp": dict(kind="crr", mode="exp", freq=2, bs=64, optim="adam"),
+    "crr_binary": dict(kind="crr", mode="binary", shared=True, freq=0, bs=32, optim="adam"),
+}
+OFFLINE = dict(N=51, hidden=16, gamma=0.97, tau=0.8, mqw=2.0, beta=0.05, ub=3.0, updates=5,
+               sample_seed=8, fixed_obs=40)
+OFFLINE_INIT_SEEDS = tuple(range(11, 31))
+
+
+def _offline_policy(v, seed):
+    from tianshou.policy import DiscreteBCQPolicy, DiscreteCQLPolicy, DiscreteCRRPolicy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.discrete import Actor, Critic
+    D, A, H, o = DQN_D, DQN_A, OFFLINE["hidden"], OFFLINE
+    torch.manual_seed(seed)
+    if v["kind"] == "cql":
+        nets = [Net(D, A, hidden_sizes=(H, H), num_atoms=o["N"])]
+    else:
+        t1 = Net(D, hidden_sizes=(H, H))
+        t2 = t1 if v.get("shared") else Net(D, hidden_sizes=(H, H))
+        second = Critic(t2, hidden_sizes=[H], last_size=A) if v["kind"] == "crr" else \
+            Actor(t2, A, hidden_sizes=[H], softmax_output=False)
+        nets = [Actor(t1, A, hidden_sizes=[H], softmax_output=False), second]
+    params = list({id(p): p for n in nets for p in n.parameters()}.values())
+    optim = torch.optim.RMSprop(params, lr=7e-4, eps=1e-5, alpha=0.99) if v["optim"] == "rms" \
+        else torch.optim.Adam(params, lr=1e-3)
+    if v["kind"] == "bcq":
+        return DiscreteBCQPolicy(nets[0], nets[1], optim, o["gamma"], v["n_step"], v["freq"],
+                                 unlikely_action_threshold=o["tau"])
+    if v["kind"] == "cql":
+        return DiscreteCQLPolicy(nets[0], optim, o["gamma"], o["N"], v["n_step"], v["freq"],
+                                 min_q_weight=o["mqw"])
+    policy = DiscreteCRRPolicy(nets[0], nets[1], optim, o["gamma"], v["mode"], o["ub"],
+                               o["beta"], o["mqw"], v["freq"], action_scaling=False,
+                               deterministic_eval=True)
+    policy.action_type = "discrete"  # what an action_space would set; the fixed forward reads it
+    return policy
+
+
+def _offline_run(v, adds, seed, reverse=False):
+    """(recorded arrays, the margins the run kept) of one variant on the reference."""
+    o = OFFLINE
+    buf = VectorReplayBuffer(DQN_E * DQN_S, DQN_E)
+    for a in adds:
+        buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}), buffer_ids=a["ids"])
+    policy = _offline_policy(v, seed)
+    out = {"init_sd_" + k: t.detach().numpy().copy() for k, t in policy.state_dict().items()}
+    chk = dict(ratio=np.inf, gap=np.inf, coef=np.inf, adv=np.inf, masked=0, clamped=0)
+    forward, process_fn, learn, sample = policy.forward, policy.process_fn, policy.learn, \
+        buf.sample_indices
+    seen = []
+
+    def rec_forward(batch, *a, **kw):
+        res = forward(batch, *a, **kw)
+        if v["kind"] == "bcq":
+            lg = res.imitation_logits.detach().double()
+            ratio = lg - lg.max(-1, keepdim=True).values
+            chk["ratio"] = min(chk["ratio"], float((ratio - policy._log_tau).abs().min()))
+            chk["masked"] += int((ratio < policy._log_tau).sum())
+        elif v["kind"] == "cql":
+            chk["gap"] = min(chk["gap"], _top2_gap(res.logits.detach().mean(2).numpy()))
+        return res
+
+    def rec_process(batch, buffer, indices):
+        batch = process_fn(batch, buffer, indices)
+        seen.append(dict(indices=np.array(indices, copy=True)))
+        if v["kind"] != "crr":
+            seen[-1]["returns"] = batch.returns.detach().numpy().copy()
+        return batch
+
+    def rec_learn(batch, **kw):
+        if v["kind"] == "crr":
+            with torch.no_grad():
+                q = policy.critic(batch.obs).double()
+                p = torch.softmax(policy.actor(batch.obs)[0].double(), -1)
+                adv = q.gather(1, torch.as_tensor(batch.act).long().unsqueeze(1)).flatten() \
+                    - (q * p).sum(-1)
+            if v["mode"] == "exp":
+                e = (adv / o["beta"]).exp()
+                chk["coef"] = min(chk["coef"], float(((e - o["ub"]).abs() / o["ub"]).min()))
+                chk["clamped"] += int((e > o["ub"]).sum())
+            elif v["mode"] == "binary":
+                chk["adv"] = min(chk["adv"], float(adv.abs().min()))
+        return learn(batch, **kw)
+
+    policy.forward, policy.process_fn, policy.learn = rec_forward, rec_process, rec_learn
+    if reverse:
+        buf.sample_indices = lambda n: sample(n)[::-1].copy()
+    np.random.seed(o["sample_seed"])
+    for u in range(o["updates"]):
+        res = policy.update(v["bs"], buf)
+        q = f"u{u}_"
+        out[q + "losses"] = np.array(list(res.values()))
+        out.update({q + k: a for k, a in seen[u].items()})
+        out.update({q + "sd_" + k: t.detach().numpy().copy()
+                    for k, t in policy.state_dict().items()})
+    out["loss_keys"] = np.array(json.dumps(list(res)))
+    policy.eval()
+    fixed = np.random.default_rng(77).standard_normal((o["fixed_obs"], DQN_D)).astype(np.float32)
+    res = policy(Batch(obs=fixed, info={}))
+    if v["kind"] == "crr":
+        chk["gap"] = min(chk["gap"], _top2_gap(res.logits.detach().numpy()))
+    out["fixed_act"] = np.array(res.act.detach() if isinstance(res.act, torch.Tensor) else res.act)
+    return out, chk
+
+
+def _offline_holds(chk):
+    return chk["ratio"] >= 1e-3 and chk["gap"] >= 1e-3 and chk["coef"] >= 1e-3 and \
+        chk["adv"] >= 1e-4
+
+
+def gen_offline():
+    adds = _dqn_adds(np.random.default_rng(41))
+    out = {"add_len": np.array([len(a["ids"]) for a in adds])}
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    out["fixed_obs"] = np.random.default_rng(77).standard_normal(
+        (OFFLINE["fixed_obs"], DQN_D)).astype(np.float32)
+    checks = {}
+    for tag, v in OFFLINE_VARIANTS.items():
+        for seed in OFFLINE_INIT_SEEDS:
+            rec, chk = _offline_run(v, adds, seed)
+            if not _offline_holds(chk):
+                continue
+            rev, _ = _offline_run(v, adds, seed, reverse=True)
+            last = f"u{OFFLINE['updates'] - 1}_sd_"
+            chk["reversed"] = max(float(np.abs(rec[k].astype(np.float64) - rev[k]).max())
+                                  for k in rec if k.startswith(last))
+            # RMSprop's early steps are compared at a measured bound, not at the Adam one
+            if v["optim"] == "rms" or chk["reversed"] <= 2.5e-7:
+                break
+        else:
+            raise AssertionError(f"{tag}: no init seed keeps the margins")
+        chk = {k: (x if np.isfinite(x) else None) for k, x in chk.items()}
+        checks[tag] = dict(seed=seed, **chk)
+        print(tag, checks[tag])
+        out.update({tag + "_" + k: a for k, a in rec.items()})
+    out["cfg"] = np.array(json.dumps(dict(E=DQN_E, S=DQN_S, D=DQN_D, A=DQN_A, variants=OFFLINE_VARIANTS,
+                                          checks=checks, **OFFLINE)))
+    _save("offline.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
@@ -3547,7 +3706,7 @@ if __name__ == "__main__":
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
                              "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn",
-                             "fqf", "bdq"]
+                             "fqf", "bdq", "offline"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -3559,6 +3718,6 @@ if __name__ == "__main__":
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
                  redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf,
-                 bdq=gen_bdq)
+                 bdq=gen_bdq, offline=gen_offline)
     for w in which:
         table[w]()
