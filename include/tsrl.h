@@ -1299,6 +1299,54 @@ int tsrl_crr_loss_fwd_bwd(const float* q, const float* logits, const int64_t* ac
                           int64_t num_actions, float* grad_q, float* grad_logits,
                           double* partials, float* loss, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The continuous offline policies (tianshou/policy/imitation/cql.py, td3_bc.py),
+ * csrc/offline_cont.hip.  All rows are contiguous f32.  Batch sums are f64 in csrc/loss_sum.h's
+ * fixed order (256 rows per workgroup, partials in block order beyond one): bit-identical
+ * between runs, no float atomics.  partials: NK * tsrl_ddpg_num_partials(rows) doubles, read
+ * and written only when that count is > 1.
+ * tsrl_cql_expand: the repeated rows of cql.py:206-220 in one launch.  With n = b R, output row
+ *   i R + j repeats source row i: actor_in [2 n, D] = repeat(obs) then repeat(obs_next);
+ *   critic_obs [3 n, D] = repeat(obs) three times; critic_act[0..n) [n, A] = fl(lo + fl(u *
+ *   fl(hi - lo))) of the uniform draw u [n, A] in [0, 1) -- the rows n..3n of the critics'
+ *   action input are not touched.  Rows move as 16-byte vectors when D % 4 == 0 and obs,
+ *   obs_next, actor_in and critic_obs are 16-byte aligned, float by float otherwise.
+ * tsrl_cql_target: out[r] = rew[r] + fl(fl(gamma (1 - done[r])) * fl(min(q1, q2)[r] -
+ *   fl(alpha[0] log_prob[r]))) (cql.py:185-194), torch's f32 evaluation order; min hands a NaN
+ *   through; done is f32 (0 or 1), alpha one device element.
+ * tsrl_cql_loss_fwd_bwd: cql.py:198-260 for both critics.  q1, q2, target [b]; v1, v2 [3, n]:
+ *   a critic's value at the random, current-policy and next-policy actions; log_pi [2, n]: the
+ *   log-probabilities of the latter two.  Per row of n, in f64: x = ((v[0] - log(0.5^act_dim)) /
+ *   T, (v[1] - log_pi[0]) / T, (v[2] - log_pi[1]) / T), lse = the max-subtracted logsumexp of
+ *   x.  cql_i = mean_n(lse_i) w T - mean_b(q_i) w; with_lagrange: a = clamp(expf(cql_log_alpha),
+ *   alpha_min, alpha_max) in f32 and cql_i <- a (cql_i - lagrange_threshold), else a = 1.
+ *   loss[i] = mean_b (q_i - target)^2 + cql_i; lagrange[0] = -(cql_1 + cql_2) / 2, lagrange[1]
+ *   = a, g_cql_log_alpha[0] = d lagrange[0] / d cql_log_alpha, 0 where the clamp is active
+ *   (all three written only with_lagrange).  g_q_i [b] = 2 (q_i - target) / b - a w / b,
+ *   g_v_i [3, n] = a w softmax(x) / n: the gradients of loss[i].  partials: 6 per workgroup
+ *   of n rows.
+ * tsrl_td3bc_actor_loss_fwd_bwd: td3_bc.py:91-96.  loss[0] = -lmbda mean(q) + mean((act -
+ *   data_act)^2) over [b, A], lmbda = alpha / mean|q| held constant; g_act = 2 (act - data_act) /
+ *   (b A), g_q = -lmbda / b.  One launch up to 256 rows, a second (the fold, which writes g_q)
+ *   beyond.  partials: 3 per workgroup of b rows.
+ * ------------------------------------------------------------------------------- */
+int tsrl_cql_expand(const float* obs, const float* obs_next, const float* u, double lo, double hi,
+                    int64_t b, int64_t repeat, int64_t obs_dim, int64_t act_dim, float* actor_in,
+                    float* critic_obs, float* critic_act, void* stream);
+int tsrl_cql_target(const float* q1, const float* q2, const float* log_prob, const float* alpha,
+                    const float* rew, const float* done, double gamma, int64_t b, float* out,
+                    void* stream);
+int tsrl_cql_loss_fwd_bwd(const float* q1, const float* q2, const float* target, const float* v1,
+                          const float* v2, const float* log_pi, const float* cql_log_alpha,
+                          double temperature, double cql_weight, double lagrange_threshold,
+                          double alpha_min, double alpha_max, int64_t act_dim, int with_lagrange,
+                          int64_t b, int64_t repeat, float* g_q1, float* g_q2, float* g_v1,
+                          float* g_v2, double* partials, float* loss, float* lagrange,
+                          float* g_cql_log_alpha, void* stream);
+int tsrl_td3bc_actor_loss_fwd_bwd(const float* q, const float* act, const float* data_act,
+                                  double alpha, int64_t b, int64_t act_dim, float* g_q,
+                                  float* g_act, double* partials, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,13 @@ _SIGS = {
                                  ctypes.c_int),
     "tsrl_crr_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _p, _p, _d, ctypes.c_int, _d, _d, _d, _i64,
                                _i64, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_cql_expand": ([_p, _p, _p, _d, _d, _i64, _i64, _i64, _i64, _p, _p, _p, _p],
+                        ctypes.c_int),
+    "tsrl_cql_target": ([_p, _p, _p, _p, _p, _p, _d, _i64, _p, _p], ctypes.c_int),
+    "tsrl_cql_loss_fwd_bwd": ([_p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _d, _i64, ctypes.c_int,
+                               _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_td3bc_actor_loss_fwd_bwd": ([_p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p],
+                                      ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:

@@ -19,8 +19,11 @@ from tianshou_amd.policy.redq import REDQPolicy
 from tianshou_amd.policy.discrete_bcq import DiscreteBCQPolicy
 from tianshou_amd.policy.discrete_cql import DiscreteCQLPolicy
 from tianshou_amd.policy.discrete_crr import DiscreteCRRPolicy
+from tianshou_amd.policy.cql import CQLPolicy
+from tianshou_amd.policy.td3_bc import TD3BCPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
            "DQNPolicy", "C51Policy", "QRDQNPolicy", "RainbowPolicy", "IQNPolicy", "FQFPolicy",
            "BranchingDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy", "DiscreteSACPolicy",
-           "REDQPolicy", "DiscreteBCQPolicy", "DiscreteCQLPolicy", "DiscreteCRRPolicy"]
+           "REDQPolicy", "DiscreteBCQPolicy", "DiscreteCQLPolicy", "DiscreteCRRPolicy",
+           "CQLPolicy", "TD3BCPolicy"]

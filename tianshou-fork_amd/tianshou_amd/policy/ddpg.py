@@ -421,10 +421,12 @@ class DDPGPolicy(BasePolicy):
         return self._result(vals if do_actor else vals[:nc], do_actor)
 
     def _backward_step(self, handle: torch.Tensor, names: Sequence[str],
-                       fas: Dict[str, Optional[FlatAdam]]) -> None:
+                       fas: Dict[str, Optional[FlatAdam]],
+                       max_norm: Optional[float] = None) -> None:
         """zero_grad, backward and optimiser step of networks ``names`` on loss ``handle``.
         Only their parameters receive gradients: the actor loss's backward runs through the
-        critic without leaving anything in the critic's gradient storage."""
+        critic without leaving anything in the critic's gradient storage.  ``max_norm``: each
+        network's gradient is first clipped to that norm (clip_grad_norm_ per network)."""
         params = []
         for name in names:
             if fas[name] is None:
@@ -435,9 +437,11 @@ class DDPGPolicy(BasePolicy):
         for name in names:
             fa = fas[name]
             if fa is None:
+                if max_norm is not None:
+                    torch.nn.utils.clip_grad_norm_(getattr(self, name).parameters(), max_norm)
                 getattr(self, name + "_optim").step()
             else:
-                fa.clip_adam(None)  # the reference clips nothing: one optimiser pass
+                fa.clip_adam(max_norm)  # None (the online policies): one optimiser pass
 
     def _step(self, fas: Dict[str, Optional[FlatAdam]], obs, act, returns, weight,
               do_actor: bool, td_out: torch.Tensor, loss_out: torch.Tensor) -> None:

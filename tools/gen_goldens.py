@@ -3699,6 +3699,180 @@ def gen_offline():
     _save("offline.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# 33. The continuous offline policies (tianshou/policy/imitation/cql.py, td3_bc.py): five
+#     update() calls per variant over gen_sac's add() stream, every draw (N(0, 1) through
+#     torch.distributions' _standard_normal clamped to +-2 as in gen_sac, torch.randn for TD3's
+#     smoothing, and the U[0, 1) behind cql.py:206-208: uniform_(lo, hi) is replaced by lo +
+#     rand * (hi - lo) on the recorded rand), the state_dict before the first and after every
+#     update, and a forward on fixed observations.  The init seed of every variant is the first
+#     of CONT_OFFLINE_INIT_SEEDS on which the reference alone keeps: every critic gradient
+#     norm that clip_grad_norm_ sees 1e-3 relative off clip_grad; the multiplier of cql_lagrange
+#     strictly inside its clamp; and the run with every sampled batch (and its draws) reversed
+#     within a quarter of the parameter bound, 2.5e-7 (gen_offline's rule).
+# --------------------------------------------------------------------------------------
+CONT_OFFLINE_VARIANTS = {
+    "cql_lagrange": dict(kind="cql", auto=True, bs=32, kw=dict(min_action=-0.5)),
+    "cql_clamped": dict(kind="cql", auto=False, bs=32, kw=dict(alpha_max=0.9)),
+    "cql_plain": dict(kind="cql", auto=False, bs=32,
+                      kw=dict(with_lagrange=False, temperature=0.7, clip_grad=0.05)),
+    "td3bc": dict(kind="td3bc", bs=32, kw=dict(update_actor_freq=2, estimation_step=3)),
+}
+CONT_OFFLINE = dict(hidden=16, gamma=0.97, tau=0.05, R=10, cql_alpha_lr=3e-3, alpha_lr=3e-3,
+                    updates=5, sample_seed=8, fixed_obs=40)
+CONT_OFFLINE_INIT_SEEDS = tuple(range(11, 31))
+
+
+def _cont_offline_policy(v, seed):
+    from tianshou.policy import CQLPolicy, TD3BCPolicy
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import Actor, ActorProb, Critic
+    D, A, H, o = DDPG_D, DDPG_A, CONT_OFFLINE["hidden"], CONT_OFFLINE
+    torch.manual_seed(seed)
+    critics = [Critic(Net(D, A, hidden_sizes=(H, H), concat=True)) for _ in range(2)]
+    if v["kind"] == "td3bc":
+        actor = Actor(Net(D, hidden_sizes=(H, H)), (A,))
+    else:
+        actor = ActorProb(Net(D, hidden_sizes=(H, H)), (A,), unbounded=True,
+                          conditioned_sigma=True)
+    opt = [torch.optim.Adam(m.parameters(), lr=1e-3) for m in (actor, *critics)]
+    args = (actor, opt[0], critics[0], opt[1], critics[1], opt[2])
+    if v["kind"] == "td3bc":
+        return TD3BCPolicy(*args, tau=o["tau"], gamma=o["gamma"], exploration_noise=None,
+                           action_scaling=False, **v["kw"])
+    alpha = 0.2
+    if v["auto"]:
+        log_alpha = torch.zeros(1, requires_grad=True)
+        alpha = (-float(A), log_alpha, torch.optim.Adam([log_alpha], lr=o["alpha_lr"]))
+    return CQLPolicy(*args, cql_alpha_lr=o["cql_alpha_lr"], tau=o["tau"], gamma=o["gamma"],
+                     alpha=alpha, num_repeat_actions=o["R"], action_scaling=False, **v["kw"])
+
+
+def _cont_offline_run(v, adds, seed, replay=None):
+    """(recorded arrays, margins) of one variant on the reference.  ``replay``: the arrays of
+    the forward run; the batches and their draws are then taken from it in reversed row order."""
+    import torch.distributions.normal as tdn
+    import tianshou.policy.imitation.cql as cql_mod
+    o, bs = CONT_OFFLINE, v["bs"]
+    buf = VectorReplayBuffer(DQN_E * DQN_S, DQN_E)
+    for a in adds:
+        buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}), buffer_ids=a["ids"])
+    policy = _cont_offline_policy(v, seed)
+    out = {"init_sd_" + k: t.detach().numpy().copy() for k, t in policy.state_dict().items()}
+    chk = dict(norm=np.inf, clipped=0, inside=True)
+    draws = dict(normal=[], uniform=[], randn=[])
+    queue = {}
+
+    def draw(kind, make):
+        if replay is None:
+            t = make()
+        else:  # the forward run's draw, rows reversed with the batch (groups of R rows stay)
+            t = torch.as_tensor(queue[kind].pop(0))
+            t = t.view(bs, -1, t.shape[-1]).flip(0).reshape(t.shape)
+        draws[kind].append(t.numpy().copy())
+        return t
+
+    real_normal, real_uniform, real_randn, real_clip = tdn._standard_normal, \
+        torch.Tensor.uniform_, torch.randn, cql_mod.clip_grad_norm_
+
+    def rec_normal(shape, dtype, device):
+        return draw("normal", lambda: real_normal(shape, dtype=dtype, device=device)
+                    .clamp(-2.0, 2.0))
+
+    def rec_uniform(self, lo=0.0, hi=1.0):
+        u = draw("uniform", lambda: torch.rand(self.shape))
+        return self.copy_(lo + u * (hi - lo))
+
+    def rec_randn(*a, **kw):
+        return draw("randn", lambda: real_randn(*a, **kw))
+
+    def rec_clip(params, max_norm, *a, **kw):
+        norm = float(real_clip(params, max_norm, *a, **kw))
+        chk["norm"] = min(chk["norm"], abs(norm - max_norm) / max_norm)
+        chk["clipped"] += int(norm > max_norm)
+        return norm
+
+    sample = buf.sample_indices
+    if replay is not None:
+        buf.sample_indices = lambda n: sample(n)[::-1].copy()
+    np.random.seed(o["sample_seed"])
+    tdn._standard_normal, torch.Tensor.uniform_, torch.randn, cql_mod.clip_grad_norm_ = \
+        rec_normal, rec_uniform, rec_randn, rec_clip
+    try:
+        for u in range(o["updates"]):
+            q = f"u{u}_"
+            if replay is not None:
+                queue = {k: [replay[f"{q}{k}{i}"] for i in range(int(replay[q + "n_" + k]))]
+                         for k in draws}
+            for k in draws:
+                draws[k].clear()
+            idx = []
+            process_fn = policy.process_fn
+            policy.process_fn = lambda b, bf, i: idx.extend(
+                (np.array(i, copy=True), process_fn(b, bf, i))) or idx[1]
+            res = policy.update(bs, buf)
+            policy.process_fn = process_fn
+            out[q + "indices"] = idx[0]
+            if v["kind"] == "td3bc":
+                out[q + "returns"] = idx[1].returns.detach().numpy().copy()
+            out[q + "losses"] = np.array(list(res.values()))
+            for k, ds in draws.items():
+                out[q + "n_" + k] = np.array(len(ds))
+                out.update({f"{q}{k}{i}": d for i, d in enumerate(ds)})
+            out.update({q + "sd_" + k: t.detach().numpy().copy()
+                        for k, t in policy.state_dict().items()})
+            if v["kind"] == "cql" and policy.with_lagrange:
+                e = float(policy.cql_log_alpha.detach().exp())
+                out[q + "cql_log_alpha"] = policy.cql_log_alpha.detach().numpy().copy()
+                chk["inside"] = chk["inside"] and policy.alpha_min < e < policy.alpha_max
+            if v["kind"] == "cql" and policy._is_auto_alpha:
+                out[q + "log_alpha"] = policy._log_alpha.detach().numpy().copy()
+    finally:
+        tdn._standard_normal, torch.Tensor.uniform_, torch.randn, cql_mod.clip_grad_norm_ = \
+            real_normal, real_uniform, real_randn, real_clip
+    out["loss_keys"] = np.array(json.dumps(list(res)))
+    policy.eval()
+    fixed = np.random.default_rng(77).standard_normal((o["fixed_obs"], DDPG_D)).astype(np.float32)
+    with torch.no_grad():
+        out["fixed_act"] = policy(Batch(obs=fixed, info={})).act.numpy().copy()
+    return out, chk
+
+
+def gen_cont_offline():
+    adds = _ddpg_adds(np.random.default_rng(43))
+    out = {"add_len": np.array([len(a["ids"]) for a in adds])}
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    out["fixed_obs"] = np.random.default_rng(77).standard_normal(
+        (CONT_OFFLINE["fixed_obs"], DDPG_D)).astype(np.float32)
+    checks = {}
+    last = f"u{CONT_OFFLINE['updates'] - 1}_sd_"
+    for tag, v in CONT_OFFLINE_VARIANTS.items():
+        for seed in CONT_OFFLINE_INIT_SEEDS:
+            rec, chk = _cont_offline_run(v, adds, seed)
+            if v["kind"] == "cql" and chk["norm"] < 1e-3:
+                continue
+            if tag == "cql_lagrange" and not chk["inside"]:
+                continue
+            if tag == "cql_plain" and chk["clipped"] != 2 * CONT_OFFLINE["updates"]:
+                continue
+            rev, _ = _cont_offline_run(v, adds, seed, replay=rec)
+            chk["reversed"] = max(float(np.abs(rec[k].astype(np.float64) - rev[k]).max())
+                                  for k in rec if k.startswith(last))
+            if chk["reversed"] <= 2.5e-7:
+                break
+        else:
+            raise AssertionError(f"{tag}: no init seed keeps the margins")
+        chk["norm"] = chk["norm"] if np.isfinite(chk["norm"]) else None
+        checks[tag] = dict(seed=seed, **chk)
+        print(tag, checks[tag])
+        out.update({tag + "_" + k: a for k, a in rec.items()})
+    out["cfg"] = np.array(json.dumps(dict(
+        E=DQN_E, S=DQN_S, D=DDPG_D, A=DDPG_A, variants=CONT_OFFLINE_VARIANTS, checks=checks,
+        **CONT_OFFLINE)))
+    _save("cont_offline.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
@@ -3706,7 +3880,7 @@ if __name__ == "__main__":
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
                              "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn",
-                             "fqf", "bdq", "offline"]
+                             "fqf", "bdq", "offline", "cont_offline"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -3718,6 +3892,6 @@ if __name__ == "__main__":
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
                  redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf,
-                 bdq=gen_bdq, offline=gen_offline)
+                 bdq=gen_bdq, offline=gen_offline, cont_offline=gen_cont_offline)
     for w in which:
         table[w]()
