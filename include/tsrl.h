@@ -1347,6 +1347,52 @@ int tsrl_td3bc_actor_loss_fwd_bwd(const float* q, const float* act, const float*
                                   double alpha, int64_t b, int64_t act_dim, float* g_q,
                                   float* g_act, double* partials, float* loss, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Fisher-vector product and conjugate gradients of NPGPolicy / TRPOPolicy (tianshou/policy/
+ * modelfree/npg.py:132-181), csrc/fvp.hip.  The actor is Linear(D,64)-Tanh-Linear(64,64)-Tanh-
+ * Linear(64,A) with a state-independent log-std; 1 <= A <= 32, any D >= 1.  Flat vectors (v,
+ * out, the CG vectors) hold n_params = A + 64 D + 64 + 4096 + 64 + 64 A + A floats, each
+ * parameter block at its offset in tsrl_fvp_net (actor.parameters() order puts the log-std
+ * first).  X: n rows of f32, ldx floats apart: ldx % 4 == 0, ldx >= roundup(D, 4), X 16-byte
+ * aligned; columns >= D are not used.
+ * With h1 = tanh(X W1^T + b1), h2 = tanh(h1 W2^T + b2) and v = (vs, V1, c1, V2, c2, V3, c3):
+ *   Rh1 = (1 - h1^2)(X V1^T + c1), Rh2 = (1 - h2^2)(Rh1 W2^T + h1 V2^T + c2),
+ *   g = (Rh2 W3^T + h2 V3^T + c3) exp(-2 log_std) / n,
+ *   dW3 = g^T h2, db3 = sum g, dz2 = (g W3)(1 - h2^2), dW2 = dz2^T h1, db2 = sum dz2,
+ *   dz1 = (dz2 W2)(1 - h1^2), dW1 = dz1^T X, db1 = sum dz1,
+ *   out = (2 vs, dW1, db1, dW2, db2, dW3, db3) + damping v:
+ * the Hessian of KL(old || new).mean() at new = old times v, plus damping v.  Products run on
+ * v_mfma_f32_32x32x2f32 (f32 operands); sums over rows are per 64-row tile, then per workgroup,
+ * then over the workgroups in order: no atomics, two calls are bitwise equal.
+ * tsrl_fvp_prepare: h1, h2 of the n rows into the workspace, once per minibatch and weights.
+ * tsrl_fvp_apply: two launches (product, fold).  Also leaves the f64 partial sums of v . out at
+ *   the start of the workspace for tsrl_cg_step.  cg_state (may be NULL): the state of a solve;
+ *   once that solve has stopped both launches return without writing.
+ * tsrl_cg_init: x = 0, r = p = b, state[0] = b . b, state[1] = 0 (state: 2 doubles).
+ * tsrl_cg_step: with z = the product of p: alpha = state[0] / p . z, x += alpha p, r -= alpha z;
+ *   r . r < residual_tol sets state[1] = 1 (x keeps this step's alpha p; a NaN does not stop);
+ *   else p = r + (r . r / state[0]) p, state[0] = r . r.  Scalars and dots are f64.  A stopped
+ *   solve's later steps change nothing.  No host read in a solve.
+ * Errors (hipErrorInvalidValue, text in tsrl_last_error): n < 1, A outside 1..32, a misaligned
+ * or short row pitch, offsets outside the flat vector, a short workspace.
+ * ------------------------------------------------------------------------------- */
+typedef struct tsrl_fvp_net {
+    const float *w1, *b1, *w2, *b2, *w3, *b3, *log_std;
+    int64_t off_sigma, off_w1, off_b1, off_w2, off_b2, off_w3, off_b3, n_params;
+} tsrl_fvp_net;
+int64_t tsrl_fvp_workspace_bytes(int64_t n, int64_t obs_dim, int64_t act_dim);
+int tsrl_fvp_prepare(const float* X, int64_t ldx, int64_t n, int64_t obs_dim, int64_t act_dim,
+                     const tsrl_fvp_net* net, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int tsrl_fvp_apply(const float* X, int64_t ldx, int64_t n, int64_t obs_dim, int64_t act_dim,
+                   const tsrl_fvp_net* net, const float* v, float* out, double damping,
+                   const double* cg_state, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+int tsrl_cg_init(const float* b, int64_t n_params, float* x, float* r, float* p, double* state,
+                 void* stream);
+int tsrl_cg_step(float* x, float* r, float* p, const float* z, int64_t n_params,
+                 double residual_tol, double* state, const void* fvp_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

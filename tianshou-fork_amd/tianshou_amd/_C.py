@@ -102,6 +102,13 @@ class TailGrads(ctypes.Structure):
     _fields_ = [(k, _p) for k in ("w2a", "b2a", "w2c", "b2c", "w3a", "b3a", "w3c", "b3c")]
 
 
+class FvpNet(ctypes.Structure):
+    """Mirror of ``tsrl_fvp_net``."""
+    _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "log_std")] + \
+               [(k, _i64) for k in ("off_sigma", "off_w1", "off_b1", "off_w2", "off_b2",
+                                    "off_w3", "off_b3", "n_params")]
+
+
 _SIGS = {
     "tsrl_version": ([], ctypes.c_char_p),
     "tsrl_last_error": ([], ctypes.c_char_p),
@@ -293,6 +300,13 @@ _SIGS = {
                                _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_td3bc_actor_loss_fwd_bwd": ([_p, _p, _p, _d, _i64, _i64, _p, _p, _p, _p, _p],
                                       ctypes.c_int),
+    "tsrl_fvp_workspace_bytes": ([_i64, _i64, _i64], _i64),
+    "tsrl_fvp_prepare": ([_p, _i64, _i64, _i64, _i64, ctypes.POINTER(FvpNet), _p, _i64, _p],
+                         ctypes.c_int),
+    "tsrl_fvp_apply": ([_p, _i64, _i64, _i64, _i64, ctypes.POINTER(FvpNet), _p, _p, _d, _p, _p,
+                        _i64, _p], ctypes.c_int),
+    "tsrl_cg_init": ([_p, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
+    "tsrl_cg_step": ([_p, _p, _p, _p, _i64, _d, _p, _p, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
