@@ -1393,6 +1393,76 @@ int tsrl_cg_init(const float* b, int64_t n_params, float* x, float* r, float* p,
 int tsrl_cg_step(float* x, float* r, float* p, const float* z, int64_t n_params,
                  double residual_tol, double* state, const void* fvp_workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Continuous BCQ (tianshou/policy/imitation/bcq.py, utils/net/continuous.py:371-488),
+ * csrc/bcq.hip.  All rows are contiguous f32 unless a pitch is named.
+ * tsrl_group_linear: the first layer of a network over G groups of R rows that share their
+ *   first D input columns:  out[g R + k, :] = act(xs[g, :] Ws^T + xo[g R + k, :] Wo^T + bias)
+ *   with xs [G, D], xo [G R, K], out [G R, H], Ws = W[:, :D] and Wo = W[:, D:] of the layer's
+ *   one weight W [H, >= D + K] (rows ldw floats apart, read in place), act = ReLU (relu != 0)
+ *   or identity.  It equals linear(cat(repeat_interleave(xs, R), xo), W, bias) without the
+ *   repeat or the concat.  Forward only.  f32 operands on v_mfma_f32_32x32x2f32: xs Ws^T +
+ *   bias is accumulated once per 32 x 32 tile and every k continues from it.  W2, bias2, out2
+ *   (all three or none): a second layer of the same shape on the same inputs in the same
+ *   launch.  Vector loads are used only where D, K, ldw and the base addresses keep every
+ *   access aligned (an odd D, or a D + K that is no multiple of 4, reads scalars).  A small G
+ *   splits the k range over tsrl_group_linear_splits(...) workgroups per tile, each
+ *   recomputing the shared product; the result does not depend on the split.
+ *   K > TSRL_GROUP_LINEAR_MAX_OWN, or G R H >= 2^31: nothing is launched or written and the
+ *   call returns TSRL_ERR_GROUP_LINEAR_SHAPE (no hipError value); the caller runs repeat + cat.
+ * tsrl_bcq_vae_sample_fwd: std = expf(clamp(log_std, -4, 15)), z = mean + fl(std noise), n
+ *   elements each (continuous.py:461-467 with the draw handed in).
+ * tsrl_bcq_vae_sample_bwd: from g_z = dLoss/dz: g_mean = g_z + c mean, g_log_std = (g_z noise
+ *   + c (std - 1 / std)) std where -4 <= log_std <= 15 and 0 outside (torch's clamp), with c =
+ *   1 / (2 n): the gradient of KL / 2 of tsrl_bcq_vae_loss_fwd_bwd.
+ * tsrl_bcq_vae_loss_fwd_bwd: bcq.py:139-142.  loss[1] = mean (act - recon)^2 over [b, A],
+ *   loss[2] = KL = mean(-log std + (std^2 + mean^2 - 1) / 2) over [b, L], loss[0] = loss[1] +
+ *   KL / 2; g_recon = 2 (recon - act) / (b A).  Sums are f64 in csrc/loss_sum.h's order;
+ *   partials: 2 * tsrl_ddpg_num_partials(b) doubles, used when that count is > 1.
+ * tsrl_bcq_perturb_fwd: out = clamp(fl(fl(phi max_action) tanhf(logits)) + act, -max_action,
+ *   max_action) over [b, A] (continuous.py:404-407).  Row r of logits starts at r *
+ *   logits_stride: A, or 0 -- one row for the whole batch, which is what the reference's
+ *   preprocess_net(...)[0] selects when the net returns a bare tensor.
+ * tsrl_bcq_perturb_bwd: g_act = g_out where the unclamped value lies in [-max_action,
+ *   max_action] and 0 outside; g_logits = that times fl(phi max_action) (1 - tanh^2): [b, A] at
+ *   stride A, and at stride 0 [A], the f64 column sums over the rows in loss_sum.h's order
+ *   (partials: A * tsrl_ddpg_num_partials(b) doubles when that count is > 1).
+ * tsrl_bcq_target: out[r] = rew[r] + fl(fl((1 - done[r]) gamma) max_k v[r R + k]), v =
+ *   fl(lmbda min(q1, q2)) + fl((1 - lmbda) max(q1, q2)) (bcq.py:161-172), torch's f32 order,
+ *   NaN handed through; q1, q2 [b R], done f32.
+ * tsrl_bcq_select_act: per group g of R rows the first index of the maximum of q (torch.argmax;
+ *   a NaN counts as the maximum) and out[g, :] = act[g R + index, :]; index (may be NULL)
+ *   receives the indices.
+ * ------------------------------------------------------------------------------- */
+#define TSRL_GROUP_LINEAR_MAX_OWN 64
+#define TSRL_ERR_GROUP_LINEAR_SHAPE 100002
+int tsrl_group_linear_splits(int64_t G, int64_t R, int64_t D, int64_t K, int64_t H,
+                             int64_t n_out);
+int tsrl_group_linear(const float* xs, const float* xo, const float* W, int64_t ldw,
+                      const float* bias, float* out, const float* W2, const float* bias2,
+                      float* out2, int64_t G, int64_t R, int64_t D, int64_t K, int64_t H,
+                      int relu, void* stream);
+int tsrl_bcq_vae_sample_fwd(const float* mean, const float* log_std, const float* noise,
+                            int64_t n, float* z, float* std, void* stream);
+int tsrl_bcq_vae_sample_bwd(const float* g_z, const float* mean, const float* log_std,
+                            const float* noise, const float* std, int64_t n, float* g_mean,
+                            float* g_log_std, void* stream);
+int tsrl_bcq_vae_loss_fwd_bwd(const float* act, const float* recon, const float* mean,
+                              const float* std, int64_t b, int64_t act_dim, int64_t latent_dim,
+                              float* g_recon, double* partials, float* loss, void* stream);
+int tsrl_bcq_perturb_fwd(const float* logits, int64_t logits_stride, const float* act,
+                         double phi, double max_action, int64_t b, int64_t act_dim, float* out,
+                         void* stream);
+int tsrl_bcq_perturb_bwd(const float* g_out, const float* logits, int64_t logits_stride,
+                         const float* act, double phi, double max_action, int64_t b,
+                         int64_t act_dim, float* g_act, float* g_logits, double* partials,
+                         void* stream);
+int tsrl_bcq_target(const float* q1, const float* q2, const float* rew, const float* done,
+                    double lmbda, double gamma, int64_t b, int64_t repeat, float* out,
+                    void* stream);
+int tsrl_bcq_select_act(const float* q, const float* act, int64_t groups, int64_t repeat,
+                        int64_t act_dim, float* out, int64_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

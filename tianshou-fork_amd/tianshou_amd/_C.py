@@ -307,6 +307,18 @@ _SIGS = {
                         _i64, _p], ctypes.c_int),
     "tsrl_cg_init": ([_p, _i64, _p, _p, _p, _p, _p], ctypes.c_int),
     "tsrl_cg_step": ([_p, _p, _p, _p, _i64, _d, _p, _p, _p], ctypes.c_int),
+    "tsrl_group_linear_splits": ([_i64, _i64, _i64, _i64, _i64, _i64], ctypes.c_int),
+    "tsrl_group_linear": ([_p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                           ctypes.c_int, _p], ctypes.c_int),
+    "tsrl_bcq_vae_sample_fwd": ([_p, _p, _p, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_bcq_vae_sample_bwd": ([_p, _p, _p, _p, _p, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_bcq_vae_loss_fwd_bwd": ([_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p],
+                                  ctypes.c_int),
+    "tsrl_bcq_perturb_fwd": ([_p, _i64, _p, _d, _d, _i64, _i64, _p, _p], ctypes.c_int),
+    "tsrl_bcq_perturb_bwd": ([_p, _p, _i64, _p, _d, _d, _i64, _i64, _p, _p, _p, _p],
+                             ctypes.c_int),
+    "tsrl_bcq_target": ([_p, _p, _p, _p, _d, _d, _i64, _i64, _p, _p], ctypes.c_int),
+    "tsrl_bcq_select_act": ([_p, _p, _i64, _i64, _i64, _p, _p, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
@@ -317,6 +329,8 @@ ERR_DUELING_ROW = 100001      # TSRL_ERR_DUELING_ROW
 DIST_MAX_N = 4096             # TSRL_DIST_MAX_N: atoms / quantiles the C51 and QR loss kernels take
 CQL_MAX_ACTIONS = 1024        # TSRL_CQL_MAX_ACTIONS: actions tsrl_cql_qr_loss_fwd_bwd stages per row
 IQN_MAX_COSINES = 256         # TSRL_IQN_MAX_COSINES: cosines tsrl_iqn_embed_fwd stages per fraction
+GROUP_LINEAR_MAX_OWN = 64     # TSRL_GROUP_LINEAR_MAX_OWN: own columns tsrl_group_linear holds per row
+ERR_GROUP_LINEAR_SHAPE = 100002  # TSRL_ERR_GROUP_LINEAR_SHAPE
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

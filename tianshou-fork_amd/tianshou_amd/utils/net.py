@@ -720,6 +720,154 @@ class Critic(_PreprocessWrapper):
         return self.last(logits)
 
 
+class Perturbation(_PreprocessWrapper):
+    """BCQ's perturbation network (continuous.py:371-407): (state, action) -> the action moved
+    by at most ``phi * max_action`` and clipped to ``[-max_action, max_action]``.
+
+    The reference indexes ``preprocess_net(...)[0]``.  Over a ``Net`` that is the logits of the
+    (logits, state) pair; over a bare ``MLP`` (examples/offline/d4rl_bcq.py) it is row 0 of the
+    output, broadcast over the batch.  ``logits`` reproduces that line as it stands."""
+
+    def __init__(self, preprocess_net: nn.Module, max_action: float, device="cpu",
+                 phi: float = 0.05):
+        super().__init__(preprocess_net, device=device)
+        self.max_action = max_action
+        self.phi = phi
+
+    def logits(self, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        return self.preprocess_net(torch.cat([state, action], -1))[0]
+
+    def forward(self, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        noise = self.phi * self.max_action * torch.tanh(self.logits(state, action))
+        return (noise + action).clamp(-self.max_action, self.max_action)
+
+
+class VAE(nn.Module):
+    """BCQ's conditional VAE over actions (continuous.py:410-488).  ``noise`` / ``latent_z``:
+    the draws handed in (BCQPolicy makes them through its hooks); None draws as the reference
+    does -- ``randn_like(std)`` on the module's device, the decoder's latent on the CPU and
+    then moved to ``device``, so a seeded CPU run reproduces the reference's stream."""
+
+    def __init__(self, encoder: nn.Module, decoder: nn.Module, hidden_dim: int, latent_dim: int,
+                 max_action: float, device="cpu"):
+        super().__init__()
+        self.encoder = encoder
+        self.mean = nn.Linear(hidden_dim, latent_dim)
+        self.log_std = nn.Linear(hidden_dim, latent_dim)
+        self.decoder = decoder
+        self.max_action = max_action
+        self.latent_dim = latent_dim
+        self.device = device
+
+    def encode(self, state: torch.Tensor, action: torch.Tensor):
+        """(mean, log_std before its clamp) of the latent."""
+        h = self.encoder(torch.cat([state, action], -1))
+        return self.mean(h), self.log_std(h)
+
+    def forward(self, state: torch.Tensor, action: torch.Tensor,
+                noise: Optional[torch.Tensor] = None):
+        mean, log_std = self.encode(state, action)
+        std = torch.exp(log_std.clamp(-4, 15))
+        latent_z = mean + std * (torch.randn_like(std) if noise is None else noise)
+        return self.decode(state, latent_z), mean, std
+
+    def decode(self, state: torch.Tensor, latent_z: Optional[torch.Tensor] = None):
+        if latent_z is None:
+            latent_z = torch.randn(state.shape[:-1] + (self.latent_dim,)).to(self.device) \
+                .clamp(-0.5, 0.5)
+        return self.max_action * torch.tanh(self.decoder(torch.cat([state, latent_z], -1)))
+
+
+def _open_chain(net: nn.Module):
+    """(Sequential, finish) of a net whose first layer grouped_first_layer can reach -- an MLP,
+    a plain Net or a Critic over one -- else None; ``finish(y)`` maps the Sequential's output
+    to what ``net(x)`` returns."""
+    if isinstance(net, Critic) and isinstance(net.preprocess, Net):
+        inner = _open_chain(net.preprocess)
+        if inner is None:
+            return None
+        return inner[0], lambda y: net.last(inner[1](y)[0])
+    if isinstance(net, Net):
+        if net.use_dueling or net.num_atoms > 1 or net.softmax or net._noisy:
+            return None
+        return net.model.model, lambda y: (y, None)
+    if isinstance(net, MLP):
+        return net.model, lambda y: y
+    return None
+
+
+def _group_match(net: nn.Module, D: int, K: int):
+    """(first Linear, relu, finish over its output) when ``net`` opens with an f32 contiguous
+    Linear of D + K inputs followed by ReLU or by nothing (no norm layer), else None."""
+    chain = _open_chain(net)
+    mods = list(chain[0]) if chain is not None else []
+    if not mods or not isinstance(mods[0], nn.Linear):
+        return None
+    lin, w = mods[0], mods[0].weight
+    if lin.in_features != D + K or lin.bias is None or not w.is_cuda or \
+            w.dtype != torch.float32 or not w.is_contiguous() or K > _C.GROUP_LINEAR_MAX_OWN:
+        return None
+    relu = len(mods) > 1 and isinstance(mods[1], nn.ReLU)
+    rest = mods[2:] if relu else mods[1:]
+    if rest and not isinstance(rest[0], nn.Linear):
+        return None
+
+    def finish(y):
+        for m in rest:
+            y = m(y)
+        return chain[1](y)
+    return lin, relu, finish
+
+
+def group_linear(xs: torch.Tensor, xo: torch.Tensor, R: int, layers: Sequence[nn.Linear],
+                 relu: bool) -> Optional[list]:
+    """act(cat(repeat_interleave(xs, R), xo) W^T + bias) for one or two Linear layers of one
+    shape as one tsrl_group_linear launch, without the repeat or the concat: xs [G, D], xo
+    [G R, K], the layers' in_features D + K.  None when the kernel declines the shape."""
+    (G, D), K, H = xs.shape, xo.shape[1], layers[0].out_features
+    outs = [torch.empty((G * R, H), dtype=torch.float32, device=xs.device) for _ in layers]
+    second = (None, None, None) if len(layers) == 1 else \
+        (_C.ptr(layers[1].weight.detach()), _C.ptr(layers[1].bias.detach()), _C.ptr(outs[1]))
+    rc = _C.lib().tsrl_group_linear(
+        _C.ptr(xs, torch.float32), _C.ptr(xo, torch.float32), _C.ptr(layers[0].weight.detach()),
+        D + K, _C.ptr(layers[0].bias.detach()), _C.ptr(outs[0]), *second, G, R, D, K, H,
+        int(relu), _C.stream_ptr(xs.device))
+    if rc == _C.ERR_GROUP_LINEAR_SHAPE:
+        return None
+    _C.check(rc, "tsrl_group_linear")
+    return outs
+
+
+def grouped_first_layer(net, xs: torch.Tensor, xo: torch.Tensor, R: int, fused: bool = True):
+    """``net(cat([xs.repeat_interleave(R, 0), xo], -1))`` for xs [G, D] and xo [G R, K]: BCQ's
+    decoder, perturbation net and critics over every observation repeated R times.  Where the
+    net opens with a matching Linear (_group_match) and no gradient is being recorded, that
+    layer runs through tsrl_group_linear, which reads each row of xs once, and the remaining
+    modules through torch; otherwise (and with ``fused`` False) the reference's repeat + cat
+    lines run.  ``net`` may be a pair of nets: both are evaluated on the same inputs, their
+    first layers in one launch when they have one shape; the result is then a pair."""
+    nets = tuple(net) if isinstance(net, (tuple, list)) else (net,)
+    ms = None
+    if fused and xs.is_cuda and xs.dim() == 2 and xo.dim() == 2 and \
+            xo.shape[0] == xs.shape[0] * R and not torch.is_grad_enabled() and all(
+                t.dtype == torch.float32 and t.is_contiguous() for t in (xs, xo)):
+        ms = [_group_match(n, xs.shape[1], xo.shape[1]) for n in nets]
+    if ms is None or any(m is None for m in ms):
+        x = torch.cat([xs.repeat_interleave(R, 0), xo], -1)
+        res = [n(x) for n in nets]
+    else:
+        together = len(ms) == 2 and ms[0][1] == ms[1][1] and \
+            ms[0][0].out_features == ms[1][0].out_features
+        if together:
+            ys = group_linear(xs, xo, R, [m[0] for m in ms], ms[0][1])
+        else:
+            ys = [(group_linear(xs, xo, R, [m[0]], m[1]) or [None])[0] for m in ms]
+        if ys is None or any(y is None for y in ys):
+            return grouped_first_layer(net, xs, xo, R, fused=False)
+        res = [m[2](y) for m, y in zip(ms, ys)]
+    return tuple(res) if isinstance(net, (tuple, list)) else res[0]
+
+
 class DiscreteActor(nn.Module):
     """Softmax actor (utils/net/discrete.py:12-71): preprocess -> MLP -> softmax unless
     softmax_output=False.  Module layout (``preprocess``, ``last``) as the reference's, so

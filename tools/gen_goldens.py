@@ -3873,6 +3873,142 @@ def gen_cont_offline():
     _save("cont_offline.npz", **out)
 
 
+# --------------------------------------------------------------------------------------
+# Continuous BCQ (tianshou/policy/imitation/bcq.py, utils/net/continuous.py:371-488) on the
+# CPU: every draw, the initial state_dict, four updates' losses and parameters, one forward.
+# --------------------------------------------------------------------------------------
+BCQ_VARIANTS = {
+    # examples/offline/d4rl_bcq.py's layout: a bare MLP under Perturbation (row-0 broadcast)
+    "example": dict(perturb="mlp", R=10, T=100, max_action=1.0),
+    "net": dict(perturb="net", R=10, T=100, max_action=1.5),
+    "single": dict(perturb="mlp", R=1, T=20, max_action=1.0),
+}
+BCQ = dict(hidden=16, vae_hidden=24, gamma=0.97, tau=0.05, lmbda=0.75, phi=0.05, bs=32,
+           updates=4, sample_seed=8, fixed_obs=5, gap=1e-4, clamp_margin=1e-3)
+BCQ_SEEDS = tuple(range(11, 41))
+
+
+def _bcq_policy(v, seed):
+    from tianshou.policy import BCQPolicy
+    from tianshou.utils.net.common import MLP, Net
+    from tianshou.utils.net.continuous import VAE, Critic, Perturbation
+    D, A, H, VH, o = DDPG_D, DDPG_A, BCQ["hidden"], BCQ["vae_hidden"], BCQ
+    torch.manual_seed(seed)
+    net_a = MLP(D + A, A, (H, H)) if v["perturb"] == "mlp" else Net(D + A, A, (H, H))
+    actor = Perturbation(net_a, max_action=v["max_action"], phi=o["phi"])
+    critics = [Critic(Net(D, A, hidden_sizes=(H, H), concat=True)) for _ in range(2)]
+    vae = VAE(MLP(D + A, hidden_sizes=(VH, VH)), MLP(D + 2 * A, A, (VH, VH)), VH, 2 * A,
+              v["max_action"])
+    opt = [torch.optim.Adam(m.parameters(), lr=1e-3) for m in (actor, *critics, vae)]
+    return BCQPolicy(actor, opt[0], critics[0], opt[1], critics[1], opt[2], vae, opt[3],
+                     gamma=o["gamma"], tau=o["tau"], lmbda=o["lmbda"],
+                     forward_sampled_times=v["T"], num_sampled_action=v["R"])
+
+
+def _bcq_run(v, adds, seed):
+    """(recorded arrays, margins) of one variant on the reference."""
+    o = BCQ
+    buf = VectorReplayBuffer(DQN_E * DQN_S, DQN_E)
+    for a in adds:
+        buf.add(Batch(info={}, **{k: x for k, x in a.items() if k != "ids"}), buffer_ids=a["ids"])
+    policy = _bcq_policy(v, seed)
+    policy.train()
+    out = {"init_sd_" + k: t.detach().numpy().copy() for k, t in policy.state_dict().items()}
+    chk = dict(clamp=np.inf, gap=np.inf)
+    draws = dict(vae=[], decode=[])
+    real_randn, real_like = torch.randn, torch.randn_like
+
+    def rec_randn(*a, **kw):
+        draws["decode"].append(real_randn(*a, **kw))
+        return draws["decode"][-1]
+
+    def rec_like(t, **kw):
+        draws["vae"].append(real_like(t, **kw))
+        return draws["vae"][-1]
+
+    seen_log_std, seen_q1 = [], []
+
+    def watch(_m, _i, y):
+        d = y.detach()
+        seen_log_std.append(d.numpy().copy())
+        chk["clamp"] = min(chk["clamp"], float((d + 4).abs().min()), float((d - 15).abs().min()))
+
+    def flush(q):
+        for k, ds in draws.items():
+            out[q + "n_" + k] = np.array(len(ds))
+            out.update({f"{q}{k}{i}": d.numpy().copy() for i, d in enumerate(ds)})
+            ds.clear()
+
+    hook = policy.vae.log_std.register_forward_hook(watch)
+    np.random.seed(o["sample_seed"])
+    torch.randn, torch.randn_like = rec_randn, rec_like
+    try:
+        for u in range(o["updates"]):
+            q = f"u{u}_"
+            seen = []
+            process_fn = policy.process_fn
+            policy.process_fn = lambda b, bf, i: (seen.append(np.array(i, copy=True)),
+                                                  process_fn(b, bf, i))[1]
+            res = policy.update(o["bs"], buf)
+            policy.process_fn = process_fn
+            out[q + "indices"] = seen[0]
+            b = buf[seen[0]]
+            for k in ("obs", "act", "rew", "done", "obs_next"):
+                out[q + k] = np.asarray(b[k]).copy()
+            out[q + "losses"] = np.array(list(res.values()))
+            out[q + "log_std"] = seen_log_std.pop()  # the VAE forward's, before its clamp
+            assert not seen_log_std
+            flush(q)
+            out.update({q + "sd_" + k: t.detach().numpy().copy()
+                        for k, t in policy.state_dict().items()})
+        out["loss_keys"] = np.array(json.dumps(list(res)))
+        policy.eval()
+        fixed = np.random.default_rng(77).standard_normal(
+            (o["fixed_obs"], DDPG_D)).astype(np.float32)
+        critic1 = policy.critic1.forward
+
+        def gap_watch(*a, **kw):
+            y = critic1(*a, **kw)
+            seen_q1.append(y.detach().flatten().numpy().copy())
+            top = torch.topk(y.detach().flatten(), min(2, y.numel())).values
+            if len(top) == 2:
+                chk["gap"] = min(chk["gap"], float(top[0] - top[1]))
+            return y
+        policy.critic1.forward = gap_watch
+        with torch.no_grad():
+            out["fixed_act"] = np.asarray(policy(Batch(obs=fixed, info={})).act).copy()
+        policy.critic1.forward = critic1
+        out["fwd_q1"] = np.stack(seen_q1)  # critic 1 over each observation's samples
+        flush("fwd_")
+    finally:
+        torch.randn, torch.randn_like = real_randn, real_like
+        hook.remove()
+    return out, chk
+
+
+def gen_bcq():
+    adds = _ddpg_adds(np.random.default_rng(47))
+    out = {"add_len": np.array([len(a["ids"]) for a in adds])}
+    for k in adds[0]:
+        out["add_" + k] = np.concatenate([a[k] for a in adds])
+    out["fixed_obs"] = np.random.default_rng(77).standard_normal(
+        (BCQ["fixed_obs"], DDPG_D)).astype(np.float32)
+    checks = {}
+    for tag, v in BCQ_VARIANTS.items():
+        for seed in BCQ_SEEDS:
+            rec, chk = _bcq_run(v, adds, seed)
+            if chk["clamp"] >= BCQ["clamp_margin"] and chk["gap"] >= BCQ["gap"]:
+                break
+        else:
+            raise AssertionError(f"{tag}: no init seed keeps the margins")
+        checks[tag] = dict(seed=seed, **chk)
+        print(tag, checks[tag])
+        out.update({tag + "_" + k: a for k, a in rec.items()})
+    out["cfg"] = np.array(json.dumps(dict(
+        E=DQN_E, S=DQN_S, D=DDPG_D, A=DDPG_A, variants=BCQ_VARIANTS, checks=checks, **BCQ)))
+    _save("bcq.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["returns", "gae", "buffer", "split", "rms", "ppo", "collector",
@@ -3880,7 +4016,7 @@ if __name__ == "__main__":
                              "stack", "ppo_discrete", "npg", "replay", "cartpole", "sched",
                              "persist", "trainer", "trainer_script", "offpolicy_trainer", "a2c",
                              "dqn", "dist_dqn", "ddpg", "sac", "dsac", "redq", "rainbow", "iqn",
-                             "fqf", "bdq", "offline", "cont_offline"]
+                             "fqf", "bdq", "offline", "cont_offline", "bcq"]
     table = dict(returns=gen_returns_known, gae=gen_gae_random, buffer=gen_buffer_traces,
                  split=gen_split, rms=gen_rms, ppo=gen_ppo, collector=gen_collector,
                  collector_fused=gen_collector_fused, collector_wide=gen_collector_wide,
@@ -3892,6 +4028,7 @@ if __name__ == "__main__":
                  a2c=gen_a2c, dqn=gen_dqn,
                  dist_dqn=gen_dist_dqn, ddpg=gen_ddpg, sac=gen_sac, dsac=gen_dsac,
                  redq=gen_redq, rainbow=gen_rainbow, iqn=gen_iqn, fqf=gen_fqf,
-                 bdq=gen_bdq, offline=gen_offline, cont_offline=gen_cont_offline)
+                 bdq=gen_bdq, offline=gen_offline, cont_offline=gen_cont_offline,
+                 bcq=gen_bcq)
     for w in which:
         table[w]()
