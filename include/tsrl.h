@@ -1463,6 +1463,57 @@ int tsrl_bcq_target(const float* q1, const float* q2, const float* rew, const fl
 int tsrl_bcq_select_act(const float* q, const float* act, int64_t groups, int64_t repeat,
                         int64_t act_dim, float* out, int64_t* index, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The discriminator of GAILPolicy (tianshou/policy/imitation/gail.py), csrc/gail.hip:
+ * d = Linear(64, 1)(tanh(Linear(64, 64)(tanh(Linear(D + A, 64)(x))))), all with biases, D, A >= 1.
+ * A logical input row r is the pair obs[io[r]], act[ia[r]] of a tsrl_gail_rows: two f32 arrays
+ * with rows ldo >= D and lda >= A floats apart, io / ia device int64 row numbers (NULL: row r;
+ * the caller keeps them inside the arrays, they may repeat).  Columns [0, D) of W1 [64, D + A]
+ * (contiguous, read in place) multiply the observation, columns [D, D + A) the action.  No
+ * concatenated or gathered row is written.  An array whose base is 16-byte aligned and whose
+ * pitch is a multiple of 4 floats is read with 16-byte loads (a padded VectorReplayBuffer
+ * storage view included; act also needs D % 4 == 0); any other 4-byte aligned array with scalar
+ * loads.  Products run on v_mfma_f32_32x32x2f32 (f32 operands).
+ * tsrl_gail_reward: rew[r] = softplus(d[r]) = max(d, 0) + log1p(exp(-|d|)) for r < n, the
+ *   reference's -logsigmoid(-d).  One launch, no workspace; n == 0 returns 0 and writes nothing.
+ * tsrl_gail_disc_step: one discriminator step over m_pi policy rows and m_exp expert rows.
+ *   g = sigmoid(d) / m_pi (policy), -sigmoid(-d) / m_exp (expert);
+ *   dW3 = g^T h2, db3 = sum g, dz2 = g w3 (1 - h2^2), dW2 = dz2^T h1, db2 = sum dz2,
+ *   dz1 = (dz2 W2)(1 - h1^2), dW1 = dz1^T x, db1 = sum dz1;
+ *   grad (64 (D + A) + 4289 floats, every element overwritten) = (dW1, db1, dW2, db2, dW3, db3),
+ *   the order of the network's parameters();
+ *   out3 = loss = mean softplus(d_pi) + mean softplus(-d_exp), acc_pi = mean(d_pi < 0),
+ *   acc_exp = mean(d_exp > 0).
+ *   Two launches (step, fold).  Sums over rows are per 64-row tile (a tile holds rows of one
+ *   kind), per workgroup, then over the workgroups in order; the loss sums and counts are f64.
+ *   No atomics: two calls on the same inputs are bitwise equal.  Rows that pad a last tile read
+ *   the last live row of their kind, so they are finite, and contribute through g = 0.
+ *   Offsets are 64-bit throughout: no limit on a pitch or an index beyond the arrays' own.
+ * Errors (hipErrorInvalidValue, text in tsrl_last_error, nothing launched): n < 0, m_pi or m_exp
+ * < 1, a count >= 2^31, D or A < 1, a pitch shorter than its rows, a base that is not 4-byte
+ * aligned, a null pointer, a workspace that is not 16-byte aligned or shorter than
+ * tsrl_gail_disc_step_workspace_bytes (0 for shapes the step does not take).
+ * ------------------------------------------------------------------------------- */
+typedef struct tsrl_gail_rows {
+    const float* obs;
+    int64_t ldo;
+    const int64_t* io;
+    const float* act;
+    int64_t lda;
+    const int64_t* ia;
+} tsrl_gail_rows;
+typedef struct tsrl_gail_net {
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+} tsrl_gail_net;
+int tsrl_gail_reward(const tsrl_gail_rows* rows, int64_t n, int64_t obs_dim, int64_t act_dim,
+                     const tsrl_gail_net* net, float* rew, void* stream);
+int64_t tsrl_gail_disc_step_workspace_bytes(int64_t m_pi, int64_t m_exp, int64_t obs_dim,
+                                            int64_t act_dim);
+int tsrl_gail_disc_step(const tsrl_gail_rows* pi, int64_t m_pi, const tsrl_gail_rows* expert,
+                        int64_t m_exp, int64_t obs_dim, int64_t act_dim, const tsrl_gail_net* net,
+                        float* grad, float* out3, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,16 @@ class FvpNet(ctypes.Structure):
                                     "off_w3", "off_b3", "n_params")]
 
 
+class GailRows(ctypes.Structure):
+    """Mirror of ``tsrl_gail_rows``."""
+    _fields_ = [("obs", _p), ("ldo", _i64), ("io", _p), ("act", _p), ("lda", _i64), ("ia", _p)]
+
+
+class GailNet(ctypes.Structure):
+    """Mirror of ``tsrl_gail_net``."""
+    _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
 _SIGS = {
     "tsrl_version": ([], ctypes.c_char_p),
     "tsrl_last_error": ([], ctypes.c_char_p),
@@ -319,6 +329,11 @@ _SIGS = {
                              ctypes.c_int),
     "tsrl_bcq_target": ([_p, _p, _p, _p, _d, _d, _i64, _i64, _p, _p], ctypes.c_int),
     "tsrl_bcq_select_act": ([_p, _p, _i64, _i64, _i64, _p, _p, _p], ctypes.c_int),
+    "tsrl_gail_reward": ([ctypes.POINTER(GailRows), _i64, _i64, _i64, ctypes.POINTER(GailNet),
+                          _p, _p], ctypes.c_int),
+    "tsrl_gail_disc_step_workspace_bytes": ([_i64, _i64, _i64, _i64], _i64),
+    "tsrl_gail_disc_step": ([ctypes.POINTER(GailRows), _i64, ctypes.POINTER(GailRows), _i64, _i64,
+                             _i64, ctypes.POINTER(GailNet), _p, _p, _p, _i64, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
