@@ -1514,6 +1514,52 @@ int tsrl_gail_disc_step(const tsrl_gail_rows* pi, int64_t m_pi, const tsrl_gail_
                         float* grad, float* out3, void* workspace, int64_t workspace_bytes,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The curiosity head of ICMPolicy (tianshou/policy/modelbased/icm.py), csrc/icm.hip, over
+ * features phi1, phi2 [M, W] (f32, rows ld1, ld2 >= W floats apart, 4-byte aligned; 16-byte
+ * loads where base and pitch allow) and actions act [M] (int64), W in {64, 128}, 1 <= A <= 32.
+ * tsrl_icm_net: the eight parameters in parameters() order, contiguous f32:
+ *   forward model wf1 [W, W + A], bf1 [W], wf2 [W, W], bf2 [W];
+ *   inverse model wi1 [W, 2 W], bi1 [W], wi2 [A, W], bi2 [A].
+ * Per row r with a = act[r]:
+ *   z_f = wf1[:, :W] phi1 + wf1[:, W + a] + bf1 (the one-hot input is a gathered column),
+ *   e = wf2 relu(z_f) + bf2 - phi2, mse = 0.5 sum e^2,
+ *   z_i = wi1[:, :W] phi1 + wi1[:, W:] phi2 + bi1, act_hat = wi2 relu(z_i) + bi2.
+ * No one-hot and no concatenated row is written.  Products run on v_mfma_f32_32x32x2f32.
+ * tsrl_icm_head_fwd: mse [M], act_hat [M, A].  One launch, no workspace.
+ * tsrl_icm_head_step: forward = mean mse, inverse = mean(logsumexp(act_hat) - act_hat[a]),
+ *   loss = ((1 - w) inverse + w forward) lr_scale with w = forward_loss_weight;
+ *   out3 = (loss, forward, inverse); the eight gradients of loss (every element of every slot
+ *   of tsrl_icm_grads overwritten; the slots need not be adjacent); d_phi1, d_phi2 [M, W]
+ *   (contiguous, 16-byte aligned) = dloss / dphi, phi2 counted both as the inverse model's
+ *   input and as the forward model's target (the reference does not detach it).
+ *   Two launches (step, fold).  Sums over rows are per 32-row tile, per workgroup, then over the
+ *   workgroups in order; the loss sums are f64.  No atomics: two calls on the same inputs are
+ *   bitwise equal.  Rows that pad a last tile read row M - 1 and contribute nothing.
+ * An act[r] outside [0, A) causes no access outside the arrays (column W + 0 is gathered): the
+ * row's mse is NaN, and so are out3 and the gradients.  (The reference raises in F.one_hot.)
+ * M == 0 returns 0 and launches nothing.
+ * Errors (hipErrorInvalidValue, text in tsrl_last_error, nothing launched): M < 0 or >= 2^31,
+ * another W, A outside [1, 32], a pitch shorter than W, a misaligned base, a null pointer, a
+ * workspace that is not 16-byte aligned or shorter than tsrl_icm_head_step_workspace_bytes (0
+ * for shapes the step does not take; at most 35 MB).
+ * ------------------------------------------------------------------------------- */
+typedef struct tsrl_icm_net {
+    const float *wf1, *bf1, *wf2, *bf2, *wi1, *bi1, *wi2, *bi2;
+} tsrl_icm_net;
+typedef struct tsrl_icm_grads {
+    float *wf1, *bf1, *wf2, *bf2, *wi1, *bi1, *wi2, *bi2;
+} tsrl_icm_grads;
+int tsrl_icm_head_fwd(const float* phi1, int64_t ld1, const float* phi2, int64_t ld2,
+                      const int64_t* act, int64_t M, int64_t W, int64_t A,
+                      const tsrl_icm_net* net, float* mse, float* act_hat, void* stream);
+int64_t tsrl_icm_head_step_workspace_bytes(int64_t M, int64_t W, int64_t A);
+int tsrl_icm_head_step(const float* phi1, int64_t ld1, const float* phi2, int64_t ld2,
+                       const int64_t* act, int64_t M, int64_t W, int64_t A,
+                       const tsrl_icm_net* net, const tsrl_icm_grads* grads, float* d_phi1,
+                       float* d_phi2, double lr_scale, double forward_loss_weight, float* out3,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

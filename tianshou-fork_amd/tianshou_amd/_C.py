@@ -119,6 +119,11 @@ class GailNet(ctypes.Structure):
     _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
+class IcmNet(ctypes.Structure):
+    """Mirror of ``tsrl_icm_net`` and of ``tsrl_icm_grads``."""
+    _fields_ = [(k, _p) for k in ("wf1", "bf1", "wf2", "bf2", "wi1", "bi1", "wi2", "bi2")]
+
+
 _SIGS = {
     "tsrl_version": ([], ctypes.c_char_p),
     "tsrl_last_error": ([], ctypes.c_char_p),
@@ -334,6 +339,12 @@ _SIGS = {
     "tsrl_gail_disc_step_workspace_bytes": ([_i64, _i64, _i64, _i64], _i64),
     "tsrl_gail_disc_step": ([ctypes.POINTER(GailRows), _i64, ctypes.POINTER(GailRows), _i64, _i64,
                              _i64, ctypes.POINTER(GailNet), _p, _p, _p, _i64, _p], ctypes.c_int),
+    "tsrl_icm_head_fwd": ([_p, _i64, _p, _i64, _p, _i64, _i64, _i64, ctypes.POINTER(IcmNet), _p,
+                           _p, _p], ctypes.c_int),
+    "tsrl_icm_head_step_workspace_bytes": ([_i64, _i64, _i64], _i64),
+    "tsrl_icm_head_step": ([_p, _i64, _p, _i64, _p, _i64, _i64, _i64, ctypes.POINTER(IcmNet),
+                            ctypes.POINTER(IcmNet), _p, _p, _d, _d, _p, _p, _i64, _p],
+                           ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:

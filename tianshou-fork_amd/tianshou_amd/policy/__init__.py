@@ -23,9 +23,10 @@ from tianshou_amd.policy.cql import CQLPolicy
 from tianshou_amd.policy.td3_bc import TD3BCPolicy
 from tianshou_amd.policy.bcq import BCQPolicy
 from tianshou_amd.policy.gail import GAILPolicy
+from tianshou_amd.policy.icm import ICMPolicy
 
 __all__ = ["BasePolicy", "PGPolicy", "A2CPolicy", "PPOPolicy", "NPGPolicy", "TRPOPolicy",
            "DQNPolicy", "C51Policy", "QRDQNPolicy", "RainbowPolicy", "IQNPolicy", "FQFPolicy",
            "BranchingDQNPolicy", "DDPGPolicy", "TD3Policy", "SACPolicy", "DiscreteSACPolicy",
            "REDQPolicy", "DiscreteBCQPolicy", "DiscreteCQLPolicy", "DiscreteCRRPolicy",
-           "CQLPolicy", "TD3BCPolicy", "BCQPolicy", "GAILPolicy"]
+           "CQLPolicy", "TD3BCPolicy", "BCQPolicy", "GAILPolicy", "ICMPolicy"]

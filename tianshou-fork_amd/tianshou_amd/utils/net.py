@@ -1147,6 +1147,38 @@ class FullQuantileFunction(ImplicitQuantileNetwork):
         return (quantiles, fractions, quantiles_tau), hidden
 
 
+class IntrinsicCuriosityModule(nn.Module):
+    """discrete.py:397-449 (arXiv:1705.05363): ``feature_net`` maps an observation to a flat
+    feature row; ``forward_model`` predicts the next row from the row and the one-hot action,
+    ``inverse_model`` the action from both rows.  ICMPolicy runs the two models on
+    csrc/icm.hip when they have the shape its matcher takes (policy/icm.py)."""
+
+    def __init__(self, feature_net: nn.Module, feature_dim: int, action_dim: int,
+                 hidden_sizes: Sequence[int] = (),
+                 device: Union[str, torch.device] = "cpu") -> None:
+        super().__init__()
+        self.feature_net = feature_net
+        self.forward_model = MLP(feature_dim + action_dim, output_dim=feature_dim,
+                                 hidden_sizes=hidden_sizes, device=device)
+        self.inverse_model = MLP(feature_dim * 2, output_dim=action_dim,
+                                 hidden_sizes=hidden_sizes, device=device)
+        self.feature_dim = feature_dim
+        self.action_dim = action_dim
+        self.device = device
+
+    def forward(self, s1, act, s2, **kwargs: Any) -> Tuple[torch.Tensor, torch.Tensor]:
+        """s1, act, s2 -> mse_loss [B], act_hat [B, action_dim]."""
+        s1 = torch.as_tensor(s1, device=self.device, dtype=torch.float32)
+        s2 = torch.as_tensor(s2, device=self.device, dtype=torch.float32)
+        phi1, phi2 = self.feature_net(s1), self.feature_net(s2)
+        act = torch.as_tensor(act, device=self.device, dtype=torch.long)
+        onehot = torch.nn.functional.one_hot(act, num_classes=self.action_dim)
+        phi2_hat = self.forward_model(torch.cat([phi1, onehot], dim=1))
+        mse_loss = 0.5 * torch.nn.functional.mse_loss(phi2_hat, phi2, reduction="none").sum(1)
+        act_hat = self.inverse_model(torch.cat([phi1, phi2], dim=1))
+        return mse_loss, act_hat
+
+
 class ActorCritic(nn.Module):
     """common.py:364-377."""
 
