@@ -1560,6 +1560,55 @@ int tsrl_icm_head_step(const float* phi1, int64_t ld1, const float* phi2, int64_
                        float* d_phi2, double lr_scale, double forward_loss_weight, float* out3,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The LSTM stack of Recurrent / RecurrentActorProb / RecurrentCritic (utils/net/common.py:288-361),
+ * csrc/lstm.hip: L layers of width H over x [B, T, Din] (f32, element (b, t, k) at
+ * x[b ldb + t ldt + k]; 16-byte loads where base and pitches allow).  tsrl_lstm_weights holds
+ * nn.LSTM's own parameters per layer, contiguous f32, gates in torch's order i, f, g, o:
+ * w_ih [4H, Din or H], w_hh [4H, H], b_ih [4H], b_hh [4H].  Per layer and step
+ *   z = w_ih in_t + w_hh h_{t-1} + b_ih + b_hh, c_t = sigm(z_f) c_{t-1} + sigm(z_i) tanh(z_g),
+ *   h_t = sigm(z_o) tanh(c_t), in_t = x_t for layer 0 and the layer below's h_t above it.
+ * State is read and written in the nets' [B, L, H] layout: element (b, l, k) of h0 / c0 at
+ * [b s0b + l s0l + k] (a null h0 or c0 is zeros), of hn / cn at [b snb + l snl + k] (either may
+ * be null).  hn[:, L - 1] is the stack's output at the last step.  Products run on
+ * v_mfma_f32_32x32x2f32; expf / tanhf are the accurate forms.
+ * tsrl_lstm_seq_fwd: one launch, a workgroup per 32 rows for every step and layer.  With a
+ *   workspace (tsrl_lstm_seq_workspace_bytes = 24 H L T B bytes: activated gates, c_t and h_t per
+ *   (layer, t, row); 16-byte aligned) it also saves what the backward needs; with a null
+ *   workspace it writes hn / cn only.
+ * tsrl_lstm_seq_bwd: from d_out [B, H] (rows ldd floats apart) = dLoss / d hn[:, L - 1], the
+ *   gradients of every parameter (every element of every slot of tsrl_lstm_grads overwritten;
+ *   b_ih and b_hh receive the same values) and, unless dx is null, dx (element (b, t, k) at
+ *   dx[b ldxb + t ldxt + k]).  Two launches: a sequential one per 32-row tile that overwrites
+ *   the workspace's gates with their gradients, then one weight-gradient launch whose every
+ *   output element is summed by one workgroup over the T B rows in order.  No atomics: two runs
+ *   on the same inputs are bitwise equal.  No gradient flows into h0 / c0 (the nets detach
+ *   them).  The workspace is consumed: one backward per training forward.
+ * Shapes: H in {64, 128}, 1 <= L <= 4, T >= 1, B >= 0, 1 <= Din <= 512, B T < 2^29; any other
+ * returns TSRL_ERR_LSTM_SHAPE (no hipError value, nothing launched): the caller runs torch's
+ * nn.LSTM.  B == 0, or no output pointer at all, returns 0 and launches nothing.  Other errors
+ * (hipErrorInvalidValue, text in tsrl_last_error): a null input or weight, a pitch or stride
+ * shorter than its row, a workspace that is misaligned or too short.
+ * ------------------------------------------------------------------------------- */
+#define TSRL_ERR_LSTM_SHAPE 100003
+typedef struct tsrl_lstm_weights {
+    const float *w_ih[4], *w_hh[4], *b_ih[4], *b_hh[4];
+} tsrl_lstm_weights;
+typedef struct tsrl_lstm_grads {
+    float *w_ih[4], *w_hh[4], *b_ih[4], *b_hh[4];
+} tsrl_lstm_grads;
+int64_t tsrl_lstm_seq_workspace_bytes(int64_t B, int64_t T, int64_t L, int64_t H);
+int tsrl_lstm_seq_fwd(const float* x, int64_t ldb, int64_t ldt, int64_t B, int64_t T, int64_t Din,
+                      int64_t L, int64_t H, const tsrl_lstm_weights* w, const float* h0,
+                      const float* c0, int64_t s0b, int64_t s0l, float* hn, float* cn,
+                      int64_t snb, int64_t snl, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int tsrl_lstm_seq_bwd(const float* x, int64_t ldb, int64_t ldt, int64_t B, int64_t T, int64_t Din,
+                      int64_t L, int64_t H, const tsrl_lstm_weights* w, const float* h0,
+                      const float* c0, int64_t s0b, int64_t s0l, const float* d_out, int64_t ldd,
+                      const tsrl_lstm_grads* grads, float* dx, int64_t ldxb, int64_t ldxt,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

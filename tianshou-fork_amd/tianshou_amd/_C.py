@@ -124,6 +124,11 @@ class IcmNet(ctypes.Structure):
     _fields_ = [(k, _p) for k in ("wf1", "bf1", "wf2", "bf2", "wi1", "bi1", "wi2", "bi2")]
 
 
+class LstmWeights(ctypes.Structure):
+    """Mirror of ``tsrl_lstm_weights`` and of ``tsrl_lstm_grads``: per layer l < 4."""
+    _fields_ = [(k, _p * 4) for k in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
 _SIGS = {
     "tsrl_version": ([], ctypes.c_char_p),
     "tsrl_last_error": ([], ctypes.c_char_p),
@@ -345,6 +350,14 @@ _SIGS = {
     "tsrl_icm_head_step": ([_p, _i64, _p, _i64, _p, _i64, _i64, _i64, ctypes.POINTER(IcmNet),
                             ctypes.POINTER(IcmNet), _p, _p, _d, _d, _p, _p, _i64, _p],
                            ctypes.c_int),
+    "tsrl_lstm_seq_workspace_bytes": ([_i64, _i64, _i64, _i64], _i64),
+    "tsrl_lstm_seq_fwd": ([_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                           ctypes.POINTER(LstmWeights), _p, _p, _i64, _i64, _p, _p, _i64, _i64,
+                           _p, _i64, _p], ctypes.c_int),
+    "tsrl_lstm_seq_bwd": ([_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                           ctypes.POINTER(LstmWeights), _p, _p, _i64, _i64, _p, _i64,
+                           ctypes.POINTER(LstmWeights), _p, _i64, _i64, _p, _i64, _p],
+                          ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
@@ -357,6 +370,7 @@ CQL_MAX_ACTIONS = 1024        # TSRL_CQL_MAX_ACTIONS: actions tsrl_cql_qr_loss_f
 IQN_MAX_COSINES = 256         # TSRL_IQN_MAX_COSINES: cosines tsrl_iqn_embed_fwd stages per fraction
 GROUP_LINEAR_MAX_OWN = 64     # TSRL_GROUP_LINEAR_MAX_OWN: own columns tsrl_group_linear holds per row
 ERR_GROUP_LINEAR_SHAPE = 100002  # TSRL_ERR_GROUP_LINEAR_SHAPE
+ERR_LSTM_SHAPE = 100003       # TSRL_ERR_LSTM_SHAPE
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

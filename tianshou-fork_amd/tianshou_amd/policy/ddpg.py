@@ -37,7 +37,8 @@ from tianshou_amd.exploration import BaseNoise, GaussianNoise
 from tianshou_amd.policy.base import BasePolicy
 from tianshou_amd.policy.flat_adam import FlatAdam
 from tianshou_amd.policy.flat_learn import (KernelGradLoss, _partials, _unit_seed, f32_rows,
-                                            flat_backward, mirror_target, replay_learn_graph,
+                                            flat_backward, has_lstm, mirror_target,
+                                            replay_learn_graph,
                                             target_mirrored)
 from tianshou_amd.utils.capture import graph_capture
 
@@ -466,7 +467,8 @@ class DDPGPolicy(BasePolicy):
     def _graph_ok(self, obs, n: int) -> bool:
         if self._graph_failed or not isinstance(obs, torch.Tensor) or not obs.is_cuda:
             return False
-        return self._use_graph(n) and all(self._flat_ready(name) for name in self._optim_order)
+        return self._use_graph(n) and all(self._flat_ready(name) for name in self._optim_order) \
+            and not has_lstm(self)
 
     def _capture(self, graph):
         """The capture context of a learn graph (utils.capture.graph_capture)."""

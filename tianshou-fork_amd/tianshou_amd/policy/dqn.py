@@ -36,7 +36,7 @@ from tianshou_amd import _C
 from tianshou_amd.data.batch import Batch
 from tianshou_amd.policy.base import BasePolicy
 from tianshou_amd.policy.flat_adam import FlatAdam
-from tianshou_amd.policy.flat_learn import (f32_rows, flat_backward, mirror_target,
+from tianshou_amd.policy.flat_learn import (f32_rows, flat_backward, has_lstm, mirror_target,
                                             replay_learn_graph, target_mirrored)
 from tianshou_amd.policy.onpolicy import _is_unit_seed, _unit_seed
 from tianshou_amd.utils.capture import graph_capture
@@ -403,10 +403,12 @@ class DQNPolicy(BasePolicy):
     # -- HIP-graph replay of one update ----------------------------------------------------------
     def _graph_ok(self, obs, n: int) -> bool:
         """Unmasked device observations, no earlier capture failure, and -- as in
-        FusedLearnMixin._learn_cat -- conv trunks only with graph_learn=True."""
+        FusedLearnMixin._learn_cat -- conv trunks only with graph_learn=True; never a model
+        with an LSTM."""
         if self._graph_failed or not isinstance(obs, torch.Tensor) or not obs.is_cuda:
             return False
-        return self._use_graph(n) and (obs.dim() == 2 or self.graph_learn is True)
+        return self._use_graph(n) and (obs.dim() == 2 or self.graph_learn is True) and \
+            not has_lstm(self)
 
     def _capture(self, graph):
         """The capture context of a learn graph (utils.capture.graph_capture)."""

@@ -46,6 +46,17 @@ def target_mirrored(old_module: torch.nn.Module, flat_old: Optional[torch.Tensor
     return all(lo <= p.data_ptr() < hi for p in old_module.parameters())
 
 
+def has_lstm(policy: torch.nn.Module) -> bool:
+    """Some network of ``policy`` holds an nn.LSTM (looked up once): its update stays off the
+    learn graphs -- the fused LSTM backward (utils/net.py _LstmLastFn) consumes a workspace
+    whose Python-side bookkeeping a replay would skip, and that replay is not verified."""
+    found = policy.__dict__.get("_has_lstm")
+    if found is None:
+        found = policy.__dict__["_has_lstm"] = any(isinstance(m, torch.nn.LSTM)
+                                                   for m in policy.modules())
+    return found
+
+
 @contextlib.contextmanager
 def flat_backward(fas: Iterable[FlatAdam], eager: bool = True):
     """``with flat_backward(fas): loss.backward(...)``.  Eager: autograd hands over each

@@ -5,6 +5,7 @@ NoisyLinear's effective parameters, its sigma gradients and the dueling combine 
 of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd and
 FractionProposalNetwork's forward tsrl_fqf_propose_fwd (csrc/dqn_dist.hip)."""
 import contextlib
+from ctypes import byref as ctypes_byref
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
 
 import numpy as np
@@ -1177,6 +1178,270 @@ class IntrinsicCuriosityModule(nn.Module):
         mse_loss = 0.5 * torch.nn.functional.mse_loss(phi2_hat, phi2, reduction="none").sum(1)
         act_hat = self.inverse_model(torch.cat([phi1, phi2], dim=1))
         return mse_loss, act_hat
+
+
+class _LstmShape(Exception):
+    """tsrl_lstm_seq_fwd returned TSRL_ERR_LSTM_SHAPE: the caller runs torch's nn.LSTM."""
+
+
+def _lstm_table(tensors, L: int) -> "_C.LstmWeights":
+    """tsrl_lstm_weights / tsrl_lstm_grads over 4 L tensors in nn.LSTM's parameter order."""
+    tab = _C.LstmWeights()
+    for l in range(L):
+        for k, name in enumerate(("w_ih", "w_hh", "b_ih", "b_hh")):
+            getattr(tab, name)[l] = _C.ptr(tensors[4 * l + k], torch.float32)
+    return tab
+
+
+def _inner_rows(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A [B, n, k] f32 tensor whose innermost rows are contiguous, as it is (any strides above
+    them go to the kernel); anything else as a contiguous f32 copy."""
+    if t is None:
+        return None
+    t = t.detach()
+    if t.dtype != torch.float32 or t.stride(2) != 1 or min(t.stride(0), t.stride(1)) < 0:
+        t = t.float().contiguous()
+    return t
+
+
+class _LstmLastFn(torch.autograd.Function):
+    """(hn, cn) [B, L, H] of an nn.LSTM stack over x [B, T, Din] from state (h0, c0) [B, L, H]
+    (None: zeros) as one tsrl_lstm_seq_fwd launch.  hn[:, L - 1] is the differentiable output
+    (the top layer's last step, what the recurrent nets read); the gradient reaching any other
+    part of hn, and cn, is ignored: the nets hand those on detached.  The backward is
+    tsrl_lstm_seq_bwd (two launches) into the parameters and, when x needs it, x.
+
+    ``train`` is the caller's ``torch.is_grad_enabled()`` (inside ``forward`` grad mode is
+    always off, and ``needs_input_grad`` follows ``requires_grad`` whatever the mode): only a
+    training forward gets a workspace; under no_grad -- collection, target forwards -- the
+    inference form runs and writes nothing but hn / cn."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, train, *weights):
+        L = len(weights) // 4
+        H = weights[1].shape[1]
+        x = _inner_rows(x)
+        h0, c0 = _inner_rows(h0), _inner_rows(c0)
+        if (h0 is None) != (c0 is None) or (h0 is not None and h0.stride() != c0.stride()):
+            h0 = None if h0 is None else h0.contiguous()
+            c0 = None if c0 is None else c0.contiguous()
+            if h0 is None or c0 is None:
+                raise ValueError("_LstmLastFn: hidden and cell come together")
+        B, T, Din = x.shape
+        dev = x.device
+        lib = _C.lib()
+        ws, nb = None, 0
+        if train and any(ctx.needs_input_grad):
+            nb = int(lib.tsrl_lstm_seq_workspace_bytes(B, T, L, H))
+            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        hn = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        cn = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        w = [p.detach() for p in weights]
+        s0 = (h0.stride(0), h0.stride(1)) if h0 is not None else (0, 0)
+        rc = lib.tsrl_lstm_seq_fwd(
+            x.data_ptr(), x.stride(0), x.stride(1), B, T, Din, L, H, ctypes_byref(_lstm_table(w, L)),
+            None if h0 is None else h0.data_ptr(), None if c0 is None else c0.data_ptr(), *s0,
+            hn.data_ptr(), cn.data_ptr(), L * H, H, None if ws is None else ws.data_ptr(), nb,
+            _C.stream_ptr(dev))
+        if rc == _C.ERR_LSTM_SHAPE:
+            raise _LstmShape()
+        _C.check(rc, "tsrl_lstm_seq_fwd")
+        ctx.save_for_backward(x, h0, c0, ws, *w)
+        ctx.nb, ctx.params = nb, weights
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(cn)
+        return hn, cn
+
+    @staticmethod
+    def backward(ctx, g_hn, g_cn):
+        x, h0, c0, ws, *w = ctx.saved_tensors
+        n_in = 4 + len(w)
+        if g_hn is None:
+            return (None,) * n_in
+        if ws is None or getattr(ctx, "spent", False):
+            raise RuntimeError("_LstmLastFn: the workspace of a forward feeds one backward")
+        ctx.spent = True
+        L, H = len(w) // 4, w[1].shape[1]
+        B, T, Din = x.shape
+        dx = torch.empty(B, T, Din, dtype=torch.float32, device=x.device) \
+            if ctx.needs_input_grad[0] else None
+        if B == 0:  # nothing is launched for an empty batch
+            return (dx, None, None, None, *(torch.zeros_like(p) for p in w))
+        g = g_hn[:, L - 1]
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) < H:
+            g = g.float().contiguous()
+        # eager flat backward (FlatAdam.release_grads): every parameter's slot of the flat
+        # gradient bucket is published while its .grad is None; the kernels overwrite every
+        # element, so they write the slots themselves and autograd has nothing to copy
+        slots = [_fresh_grad_slot(p) for p in ctx.params]
+        direct = not torch.is_grad_enabled() and all(s is not None for s in slots)
+        grads = slots if direct else [torch.empty_like(p) for p in w]
+        s0 = (h0.stride(0), h0.stride(1)) if h0 is not None else (0, 0)
+        _C.check(_C.lib().tsrl_lstm_seq_bwd(
+            x.data_ptr(), x.stride(0), x.stride(1), B, T, Din, L, H, ctypes_byref(_lstm_table(w, L)),
+            None if h0 is None else h0.data_ptr(), None if c0 is None else c0.data_ptr(), *s0,
+            g.data_ptr(), g.stride(0), ctypes_byref(_lstm_table(grads, L)),
+            None if dx is None else dx.data_ptr(), T * Din, Din, ws.data_ptr(), ctx.nb,
+            _C.stream_ptr(x.device)), "tsrl_lstm_seq_bwd")
+        if direct:
+            for p, s in zip(ctx.params, slots):
+                p.grad = s  # the slot now holds this backward's gradient
+            return (dx,) + (None,) * (n_in - 1)
+        return (dx, None, None, None, *grads)
+
+
+def _fresh_grad_slot(p: torch.Tensor) -> Optional[torch.Tensor]:
+    """The flat-bucket slot FlatAdam.release_grads() published for ``p`` while its .grad is None
+    (net_atari's _FlattenLinear reads it the same way), when a kernel may write the gradient
+    there: dense f32 of p's shape on the device, no gradient hooks on p.  None otherwise."""
+    g = getattr(p, "_tsrl_flat_slot", None) if p.grad is None else None
+    if (g is None or g.requires_grad or not g.is_cuda or g.dtype != torch.float32 or
+            g.shape != p.shape or not g.is_contiguous() or p._backward_hooks or
+            getattr(p, "_post_accumulate_grad_hooks", None)):
+        return None
+    return g
+
+
+def _owns_storage(p: torch.Tensor) -> bool:
+    return p.untyped_storage().nbytes() == p.numel() * p.element_size()
+
+
+class _RecurrentBase(nn.Module):
+    """What Recurrent, RecurrentActorProb and RecurrentCritic share: an ``nn.LSTM`` named ``nn``
+    (the parameter holder, state_dict keys ``nn.weight_ih_l0`` ..., and the torch leg) and the
+    stack's last step from [bsz, len, dim] rows.  ``fused`` (default True): on a HIP device the
+    stack runs as ``_LstmLastFn`` over csrc/lstm.hip, reading nn.LSTM's parameters where they
+    lie -- also as views of a flat optimiser buffer (policy/flat_adam.py) -- and the state in
+    its [bsz, L, H] layout; a shape the kernels do not take (tsrl.h) runs the torch leg.
+
+    ``flatten_parameters()`` moves parameter storage on the GPU, which would unbind a flat
+    optimiser pass: the fused leg never calls it, and the torch leg calls it only while every
+    parameter still owns its storage (once they are views of one buffer, a flat optimiser's
+    or flatten_parameters' own, there is nothing left for it to do)."""
+
+    def _make_lstm(self, input_size: int, hidden: int, layer_num: int, fused: bool) -> None:
+        self.nn = nn.LSTM(input_size=input_size, hidden_size=hidden, num_layers=layer_num,
+                          batch_first=True)
+        self.fused = fused
+
+    def _input(self, x) -> torch.Tensor:
+        """``x`` on the net's device in the parameters' dtype (f32, as the reference casts,
+        unless the module was converted)."""
+        return torch.as_tensor(x, device=self.device, dtype=self.nn.weight_ih_l0.dtype)
+
+    def _last(self, obs: torch.Tensor, state) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        """(top layer's h at the last step [bsz, H], {"hidden", "cell"} [bsz, L, H] detached)."""
+        if state is not None and not all(k in state for k in ("hidden", "cell")):  # dict or Batch
+            raise ValueError("Expected to find keys 'hidden' and 'cell' but instead found "
+                             f"{list(state.keys())}")
+        lstm = self.nn
+        if self.fused and obs.is_cuda and obs.dim() == 3 and lstm.weight_ih_l0.is_cuda and \
+                lstm.weight_ih_l0.dtype == torch.float32:
+            try:
+                h0, c0 = (None, None) if state is None else (state["hidden"], state["cell"])
+                hn, cn = _LstmLastFn.apply(obs, h0, c0, torch.is_grad_enabled(),
+                                           *lstm._flat_weights)
+                return hn[:, -1], {"hidden": hn.detach(), "cell": cn}
+            except _LstmShape:
+                pass
+        if all(_owns_storage(p) for p in lstm._flat_weights):
+            lstm.flatten_parameters()
+        if state is None:
+            out, (hidden, cell) = lstm(obs)
+        else:
+            # the stack data is [bsz, len, ...]; torch's rnn needs the state as [len, bsz, ...]
+            out, (hidden, cell) = lstm(obs, (state["hidden"].transpose(0, 1).contiguous(),
+                                             state["cell"].transpose(0, 1).contiguous()))
+        return out[:, -1], {"hidden": hidden.transpose(0, 1).detach(),
+                            "cell": cell.transpose(0, 1).detach()}
+
+
+class Recurrent(_RecurrentBase):
+    """common.py:288-361: fc1 -> LSTM stack -> fc2 on the last step.  ``obs`` is [bsz, len, dim]
+    in training and [bsz, dim] in evaluation (read as len 1); returns (logits, {"hidden",
+    "cell"}) with [bsz, L, H] detached state."""
+
+    def __init__(self, layer_num: int, state_shape, action_shape,
+                 device: Union[str, int, torch.device] = "cpu", hidden_layer_size: int = 128,
+                 fused: bool = True) -> None:
+        super().__init__()
+        self.device = device
+        self._make_lstm(hidden_layer_size, hidden_layer_size, layer_num, fused)
+        self.fc1 = Linear(int(np.prod(state_shape)), hidden_layer_size)
+        self.fc2 = Linear(hidden_layer_size, int(np.prod(action_shape)))
+
+    def forward(self, obs, state: Optional[Dict[str, torch.Tensor]] = None, **kwargs: Any):
+        obs = self._input(obs)
+        if len(obs.shape) == 2:
+            obs = obs.unsqueeze(-2)
+        last, state = self._last(self.fc1(obs), state)
+        return self.fc2(last), state
+
+
+class RecurrentActorProb(_RecurrentBase):
+    """continuous.py:238-319: LSTM stack over the observations, mu / sigma on the last step;
+    returns ((mu, sigma), {"hidden", "cell"})."""
+
+    def __init__(self, layer_num: int, state_shape, action_shape, hidden_layer_size: int = 128,
+                 max_action: float = 1.0, device: Union[str, int, torch.device] = "cpu",
+                 unbounded: bool = False, conditioned_sigma: bool = False,
+                 fused: bool = True) -> None:
+        super().__init__()
+        if unbounded and not np.isclose(max_action, 1.0):
+            import warnings
+            warnings.warn("Note that max_action input will be discarded when unbounded is True.")
+            max_action = 1.0
+        self.device = device
+        self._make_lstm(int(np.prod(state_shape)), hidden_layer_size, layer_num, fused)
+        output_dim = int(np.prod(action_shape))
+        self.mu = Linear(hidden_layer_size, output_dim)
+        self._c_sigma = conditioned_sigma
+        if conditioned_sigma:
+            self.sigma = Linear(hidden_layer_size, output_dim)
+        else:
+            self.sigma_param = nn.Parameter(torch.zeros(output_dim, 1))
+        self.max_action = max_action
+        self._unbounded = unbounded
+
+    def forward(self, obs, state: Optional[Dict[str, torch.Tensor]] = None,
+                info: Dict[str, Any] = {}):
+        obs = self._input(obs)
+        if len(obs.shape) == 2:
+            obs = obs.unsqueeze(-2)
+        logits, state = self._last(obs, state)
+        mu = self.mu(logits)
+        if not self._unbounded:
+            mu = self.max_action * torch.tanh(mu)
+        if self._c_sigma:
+            sigma = torch.clamp(self.sigma(logits), min=SIGMA_MIN, max=SIGMA_MAX).exp()
+        else:
+            shape = [1] * len(mu.shape)
+            shape[1] = -1
+            sigma = (self.sigma_param.view(shape) + torch.zeros_like(mu)).exp()
+        return (mu, sigma), state
+
+
+class RecurrentCritic(_RecurrentBase):
+    """continuous.py:322-368: LSTM stack over [bsz, len, dim] observations, fc2 on the last step
+    (and the action, when given)."""
+
+    def __init__(self, layer_num: int, state_shape, action_shape=[0],
+                 device: Union[str, int, torch.device] = "cpu", hidden_layer_size: int = 128,
+                 fused: bool = True) -> None:
+        super().__init__()
+        self.state_shape = state_shape
+        self.action_shape = action_shape
+        self.device = device
+        self._make_lstm(int(np.prod(state_shape)), hidden_layer_size, layer_num, fused)
+        self.fc2 = Linear(hidden_layer_size + int(np.prod(action_shape)), 1)
+
+    def forward(self, obs, act=None, info: Dict[str, Any] = {}) -> torch.Tensor:
+        obs = self._input(obs)
+        assert len(obs.shape) == 3
+        obs, _ = self._last(obs, None)
+        if act is not None:
+            obs = torch.cat([obs, self._input(act)], dim=1)
+        return self.fc2(obs)
 
 
 class ActorCritic(nn.Module):
