@@ -1609,6 +1609,39 @@ int tsrl_lstm_seq_bwd(const float* x, int64_t ldb, int64_t ldt, int64_t B, int64
                       const tsrl_lstm_grads* grads, float* dx, int64_t ldxb, int64_t ldxt,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The critic ensemble of REDQPolicy (utils/net.py: Critic over Net(concat=True), every layer an
+ * EnsembleLinear), csrc/ensemble.hip.  tsrl_ens_net holds the six parameters where
+ * EnsembleLinear keeps them, contiguous f32: w1 [E, D + A, H], b1 [E, 1, H], w2 [E, H, H], b2
+ * [E, 1, H], w3 [E, H, 1], b3 [E, 1, 1].  Per member e and row r
+ *   q[e, r] = w3[e]^T relu(w2[e]^T relu(w1[e]^T [obs[r] | act[r]] + b1[e]) + b2[e]) + b3[e]
+ * with obs [b, D] and act [b, A] two f32 arrays, rows ldo and lda floats apart; no concatenated
+ * row is written and no weight is copied or transposed.  Products run on v_mfma_f32_32x32x2f32.
+ * tsrl_ens_critic_fwd: one launch, no workspace, forward only.  Without members: q [E, b].
+ *   With members (S int32 indices in [0, E) on the device, members_host the same list on the
+ *   host, which is what is validated): only those members are computed, q [S, b], row s member
+ *   members[s]; a repeated index is computed twice.  Two calls on the same inputs are bitwise
+ *   equal, and a member's row does not depend on which other members are asked for.  Rows that
+ *   pad a last 32-row tile read row b - 1 and write nothing.  No host synchronisation: legal
+ *   inside a captured graph.
+ * Shapes: H in {128, 256}, D >= 1, A >= 0, D + A <= TSRL_ENS_MAX_IN, 1 <= E <=
+ * TSRL_ENS_MAX_MEMBERS, 1 <= b < 2^31; any other returns TSRL_ERR_ENS_SHAPE (no hipError value,
+ * nothing launched or written): the caller runs the torch lines.  Other errors
+ * (hipErrorInvalidValue, text in tsrl_last_error, nothing launched): a null pointer, a pitch
+ * shorter than its row, members without members_host or the reverse, S outside [1, E], an index
+ * outside [0, E).
+ * ------------------------------------------------------------------------------- */
+#define TSRL_ENS_MAX_IN 512
+#define TSRL_ENS_MAX_MEMBERS 64
+#define TSRL_ERR_ENS_SHAPE 100004
+typedef struct tsrl_ens_net {
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+} tsrl_ens_net;
+int tsrl_ens_critic_fwd(const float* obs, int64_t ldo, const float* act, int64_t lda, int64_t b,
+                        int64_t D, int64_t A, int64_t H, int64_t E, const tsrl_ens_net* net,
+                        const int32_t* members, const int32_t* members_host, int64_t S, float* q,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

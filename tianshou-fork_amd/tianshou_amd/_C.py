@@ -124,6 +124,11 @@ class IcmNet(ctypes.Structure):
     _fields_ = [(k, _p) for k in ("wf1", "bf1", "wf2", "bf2", "wi1", "bi1", "wi2", "bi2")]
 
 
+class EnsNet(ctypes.Structure):
+    """Mirror of ``tsrl_ens_net``."""
+    _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
 class LstmWeights(ctypes.Structure):
     """Mirror of ``tsrl_lstm_weights`` and of ``tsrl_lstm_grads``: per layer l < 4."""
     _fields_ = [(k, _p * 4) for k in ("w_ih", "w_hh", "b_ih", "b_hh")]
@@ -358,6 +363,8 @@ _SIGS = {
                            ctypes.POINTER(LstmWeights), _p, _p, _i64, _i64, _p, _i64,
                            ctypes.POINTER(LstmWeights), _p, _i64, _i64, _p, _i64, _p],
                           ctypes.c_int),
+    "tsrl_ens_critic_fwd": ([_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64,
+                             ctypes.POINTER(EnsNet), _p, _p, _i64, _p, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
@@ -371,6 +378,10 @@ IQN_MAX_COSINES = 256         # TSRL_IQN_MAX_COSINES: cosines tsrl_iqn_embed_fwd
 GROUP_LINEAR_MAX_OWN = 64     # TSRL_GROUP_LINEAR_MAX_OWN: own columns tsrl_group_linear holds per row
 ERR_GROUP_LINEAR_SHAPE = 100002  # TSRL_ERR_GROUP_LINEAR_SHAPE
 ERR_LSTM_SHAPE = 100003       # TSRL_ERR_LSTM_SHAPE
+ERR_ENS_SHAPE = 100004        # TSRL_ERR_ENS_SHAPE
+ENS_WIDTHS = (128, 256)       # hidden widths tsrl_ens_critic_fwd takes
+ENS_MAX_IN = 512              # TSRL_ENS_MAX_IN: obs + act columns
+ENS_MAX_MEMBERS = 64          # TSRL_ENS_MAX_MEMBERS
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

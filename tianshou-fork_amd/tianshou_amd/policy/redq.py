@@ -25,8 +25,18 @@ path, f32 device ``batch.weight`` and actions), and ``loss/actor`` is a float --
 returns a 1-tuple because of a stray comma (redq.py:195).  ``fused = False`` is the reference's
 op sequence, the comparison leg and the CPU path.
 
-Not built: evaluating only the sampled subset of target critics, fusing the ensemble's H -> 1
-head with the loss, a hand-written ensemble GEMM, data-parallel REDQ and a fused collect step.
+``fused_ensemble`` (off by default; with ``fused``): ``_target_q`` evaluates only the drawn
+subset of target critics, as one ``tsrl_ens_critic_fwd`` launch (csrc/ensemble.hip through
+``utils.net.ensemble_critic``) for ensembles of hidden widths (128, 128) or (256, 256), and
+hands ``tsrl_redq_target`` the [subset, b] result with the identity subset.  On the graph leg it
+saves 0.10-0.15 ms per update beyond the run-to-run spread at both bench shapes and both step
+kinds; on the eager leg the medians improve as much but stay inside that leg's spread, hence the
+default (profiles/redq_ensemble_bench.log).  The learn step's three ensemble forwards and its
+backward stay torch's batched GEMMs.
+
+Not built: the ensemble's backward and its learn-step forwards in HIP, widths other than 128 /
+256, fusing the ensemble's H -> 1 head with the loss, bf16 operands, data-parallel REDQ and a
+fused collect step.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -40,6 +50,7 @@ from tianshou_amd.exploration import BaseNoise
 from tianshou_amd.policy.ddpg import DDPGPolicy
 from tianshou_amd.policy.flat_learn import KernelGradLoss, _partials
 from tianshou_amd.policy.sac import _rows, _SquashedGaussianMixin, sac_sample
+from tianshou_amd.utils.net import ensemble_critic
 
 TARGET_MODES = {"min": 0, "mean": 1}
 
@@ -186,6 +197,7 @@ class REDQPolicy(_SquashedGaussianMixin, DDPGPolicy):
             raise ValueError("Unsupported mode of Q target computing.")
         self.critic_gradient_step = 0
         self.actor_delay = actor_delay
+        self.fused_ensemble = False
 
     # -- process_fn -----------------------------------------------------------------------------
     def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
@@ -194,6 +206,13 @@ class REDQPolicy(_SquashedGaussianMixin, DDPGPolicy):
         obs_next = self._obs_next(buffer, indices)
         res = self(Batch(obs_next=obs_next, info=Batch()), input="obs_next")
         idx = np.random.choice(self.ensemble_size, self.subset_size, replace=False)
+        if self.fused and self.fused_ensemble and isinstance(obs_next, torch.Tensor) \
+                and obs_next.is_cuda:
+            # only the drawn members are evaluated; the [S, b, 1] result is its own subset
+            with torch.no_grad():
+                qs = ensemble_critic(self.critics_old, obs_next, res.act, members=idx)
+            return redq_target_device(qs, np.arange(len(idx)), self.target_mode, res.log_prob,
+                                      self._alpha_tensor(qs.device))
         qs = self.critics_old(obs_next, res.act)
         if self.fused and qs.is_cuda:
             return redq_target_device(qs, idx, self.target_mode, res.log_prob,

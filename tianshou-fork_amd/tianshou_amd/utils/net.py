@@ -3,7 +3,9 @@ tianshou 0.5.1 checkpoints (utils/net/common.py:56-285, continuous.py:87-235,
 discrete.py:12-121, 319-394).  The GEMMs run through PyTorch-ROCm (hipBLASLt) on the GPU;
 NoisyLinear's effective parameters, its sigma gradients and the dueling combine are the kernels
 of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd and
-FractionProposalNetwork's forward tsrl_fqf_propose_fwd (csrc/dqn_dist.hip)."""
+FractionProposalNetwork's forward tsrl_fqf_propose_fwd (csrc/dqn_dist.hip); ``ensemble_critic``
+evaluates an EnsembleLinear critic, or a subset of its members, as one tsrl_ens_critic_fwd launch
+(csrc/ensemble.hip) where no gradient is recorded."""
 import contextlib
 from ctypes import byref as ctypes_byref
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
@@ -867,6 +869,67 @@ def grouped_first_layer(net, xs: torch.Tensor, xo: torch.Tensor, R: int, fused: 
             return grouped_first_layer(net, xs, xo, R, fused=False)
         res = [m[2](y) for m, y in zip(ms, ys)]
     return tuple(res) if isinstance(net, (tuple, list)) else res[0]
+
+
+def _ensemble_match(critic: nn.Module, D: int, A: int):
+    """The three EnsembleLinear layers of ``critic`` when it is exactly Critic(Net(concat=True))
+    over EnsembleLinear(D + A, H)-ReLU-EnsembleLinear(H, H)-ReLU with ``last`` one
+    EnsembleLinear(H, 1), all f32, contiguous and on the GPU; else None."""
+    if not (isinstance(critic, Critic) and isinstance(critic.preprocess, Net)
+            and isinstance(critic.last, MLP)) or critic.last.flatten_input:
+        return None
+    net = critic.preprocess
+    if net.use_dueling or net.num_atoms > 1 or net.softmax or net._noisy:
+        return None
+    mods = list(net.model.model) + list(critic.last.model)
+    if len(mods) != 5 or not all(isinstance(mods[i], EnsembleLinear) for i in (0, 2, 4)) or \
+            not all(type(mods[i]) is nn.ReLU for i in (1, 3)):
+        return None
+    l1, l2, l3 = mods[0], mods[2], mods[4]
+    (E, din, H) = l1.weight.shape
+    if din != D + A or tuple(l2.weight.shape) != (E, H, H) or tuple(l3.weight.shape) != (E, H, 1) \
+            or H not in _C.ENS_WIDTHS or din > _C.ENS_MAX_IN or E > _C.ENS_MAX_MEMBERS:
+        return None
+    for layer in (l1, l2, l3):
+        for p in (layer.weight, layer.bias):
+            if p is None or not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                return None
+    return l1, l2, l3
+
+
+def ensemble_critic(critic, obs, act, members=None, fused: bool = True) -> torch.Tensor:
+    """``critic(obs, act)`` [E, b, 1] of an ensemble critic, or with ``members`` (a sequence of
+    S member indices) ``critic(obs, act)[members]`` [S, b, 1].  Where the critic is the
+    EnsembleLinear / ReLU stack that _ensemble_match opens, obs and act are f32 GPU tensors and
+    no gradient is being recorded, this is one tsrl_ens_critic_fwd launch that reads obs and act
+    where they lie (no concatenated row) and computes only the members asked for; for anything
+    else -- another activation, a norm layer, another depth, a width the kernel declines, CPU
+    tensors, a recorded gradient, ``fused`` False -- the torch lines run."""
+    idx = None if members is None else np.ascontiguousarray(
+        np.asarray(members).reshape(-1), dtype=np.int32)
+    m = None
+    if fused and not torch.is_grad_enabled() and all(
+            isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2
+            for t in (obs, act)) and len(obs) == len(act) > 0:
+        x, a = (t.flatten(1) for t in (obs, act))
+        x, a = (t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+                for t in (x, a))
+        m = _ensemble_match(critic, x.shape[1], a.shape[1])
+    if m is not None:
+        (E, _, H), b = m[0].weight.shape, len(x)
+        params = _C.EnsNet(*(_C.ptr(p.detach()) for layer in m for p in (layer.weight, layer.bias)))
+        dev_idx = None if idx is None else torch.as_tensor(idx, device=x.device)
+        q = torch.empty((E if idx is None else idx.size, b, 1), dtype=torch.float32,
+                        device=x.device)
+        rc = _C.lib().tsrl_ens_critic_fwd(
+            _C.ptr_rows(x), x.stride(0), _C.ptr_rows(a), a.stride(0), b, x.shape[1], a.shape[1],
+            H, E, ctypes_byref(params), _C.ptr(dev_idx), None if idx is None else idx.ctypes.data,
+            0 if idx is None else idx.size, _C.ptr(q), _C.stream_ptr(x.device))
+        if rc != _C.ERR_ENS_SHAPE:
+            _C.check(rc, "tsrl_ens_critic_fwd")
+            return q
+    q = critic(obs, act)
+    return q if idx is None else q[torch.as_tensor(idx, dtype=torch.long, device=q.device)]
 
 
 class DiscreteActor(nn.Module):

@@ -23,7 +23,8 @@ delay.  "update_ms_at_delay_20" weighs their means 19 : 1, the example's actor_d
 Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), "eager"
 (graph_learn=False: the fused kernels and the flat Adam passes launched eagerly) and "torch"
 (fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
-update), the torch leg --torch-runs times to show its spread.
+update), the torch leg --torch-runs times to show its spread.  --redq-ensemble-ab RUNS: REDQ's
+graph and eager legs RUNS times each with ``fused_ensemble`` on and off, alternating.
 
 Prints one JSON line per (policy, shape, leg, run)."""
 import argparse
@@ -45,6 +46,9 @@ ap.add_argument("--updates", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--torch-runs", type=int, default=3)
 ap.add_argument("--redq-actor-delay", type=int, default=2)
+ap.add_argument("--redq-ensemble-ab", type=int, default=0, metavar="RUNS",
+                help="REDQ's graph and eager legs RUNS times each with fused_ensemble on and "
+                     "off, alternating (on, off, on, ...) in this one process")
 args = ap.parse_args()
 
 from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
@@ -172,8 +176,14 @@ for kind in args.policies.split(","):
             raise SystemExit(f"config {name} does not fit policy {kind}")
         buf = fill(cfg)
         for leg in args.legs.split(","):
-            for run in range(args.torch_runs if leg == "torch" else 1):
+            variants = [(run, None) for run in range(args.torch_runs if leg == "torch" else 1)]
+            if kind == "redq" and leg != "torch" and args.redq_ensemble_ab:
+                variants = [(run, on) for run in range(args.redq_ensemble_ab)
+                            for on in (True, False)]
+            for run, ensemble in variants:
                 policy = make_policy(kind, cfg, leg)
+                if ensemble is not None:
+                    policy.fused_ensemble = ensemble
                 np.random.seed(0)
                 torch.manual_seed(1)
                 ms, kinds, last = [], [], None
@@ -202,6 +212,7 @@ for kind in args.policies.split(","):
                     "policy": kind, "config": name, "leg": leg, "run": run,
                     "batch": cfg["batch"], "obs": cfg["D"], "act": cfg["A"],
                     "updates": args.updates, **timing,
+                    **({} if ensemble is None else {"fused_ensemble": ensemble}),
                     "graphs": len(policy._learn_graphs),
                     "flat_optimiser": bool(policy._flats) and all(
                         policy._flat_ready(n) for n in policy._optim_order),
