@@ -1642,6 +1642,42 @@ int tsrl_ens_critic_fwd(const float* obs, int64_t ldo, const float* act, int64_t
                         const int32_t* members, const int32_t* members_host, int64_t S, float* q,
                         void* stream);
 
+/* Training the ensemble: the saving forward and the backward, same shapes, layouts and errors.
+ * The workspace is caller-provided device memory at a 16-byte boundary of at least
+ * tsrl_ens_workspace_bytes(b, H, E, A) bytes (0 for a non-positive size): h1 | h2 | dz1 | dz2,
+ * each [E, b, H] f32, then per-member action-gradient partials [E, b, A].
+ * tsrl_ens_critic_fwd_save: tsrl_ens_critic_fwd over all members (the same kernel body: q [E, b]
+ *   is bitwise its q) that also writes the post-ReLU h1 and h2 to the workspace.  One launch.
+ * tsrl_ens_critic_bwd: consumes dq [E, b] (dense) and the workspace of a saving forward on the same
+ *   obs, act and net.  Chain launch: dz2 = (dq w3^T) o (h2 > 0), dz1 = (dz2 w2^T) o (h1 > 0)
+ *   into the workspace and, with da, the per-member da_e = dz1 w1[e, D:D+A, :]^T.  With grads
+ *   (six dense arrays shaped like the parameters, e.g. slots of a flat gradient bucket), a
+ *   second launch OVERWRITES them with dW_l = in_l^T dz_l and db_l = sum_r dz_l (layer 3: h2^T
+ *   dq, sum_r dq); layer 1 reads obs and act where they lie.  With da ([b, A], rows ldda floats
+ *   apart), a last small launch overwrites it with the sum of the partials in member order.
+ *   grads null: da only (the actor step); da null: the weights only (the critic step); both null
+ *   is an error.  The observation gradient is not computed.  No atomics: every sum has a fixed
+ *   order and two calls on the same inputs are bitwise equal.  Rows that pad a last tile
+ *   contribute exact zeros and write nothing.  No host synchronisation: legal inside a captured
+ *   graph.
+ * TSRL_ERR_ENS_SHAPE (nothing launched or written): the forward's shape set, and da asked for
+ * with A outside [1, TSRL_ENS_MAX_ACT_GRAD] (the action lines the chain launch stages).
+ * hipErrorInvalidValue (text in tsrl_last_error, nothing launched): a null pointer, a short
+ * pitch, a workspace that is null, unaligned or too small. */
+#define TSRL_ENS_MAX_ACT_GRAD 64
+typedef struct tsrl_ens_grads {
+    float *w1, *b1, *w2, *b2, *w3, *b3;
+} tsrl_ens_grads;
+int64_t tsrl_ens_workspace_bytes(int64_t b, int64_t H, int64_t E, int64_t A);
+int tsrl_ens_critic_fwd_save(const float* obs, int64_t ldo, const float* act, int64_t lda,
+                             int64_t b, int64_t D, int64_t A, int64_t H, int64_t E,
+                             const tsrl_ens_net* net, float* q, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int tsrl_ens_critic_bwd(const float* obs, int64_t ldo, const float* act, int64_t lda, int64_t b,
+                        int64_t D, int64_t A, int64_t H, int64_t E, const tsrl_ens_net* net,
+                        const float* dq, const tsrl_ens_grads* grads, float* da, int64_t ldda,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

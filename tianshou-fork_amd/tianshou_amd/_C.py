@@ -119,6 +119,11 @@ class GailNet(ctypes.Structure):
     _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
+class EnsGrads(ctypes.Structure):
+    """Mirror of ``tsrl_ens_grads``."""
+    _fields_ = [(k, _p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
 class IcmNet(ctypes.Structure):
     """Mirror of ``tsrl_icm_net`` and of ``tsrl_icm_grads``."""
     _fields_ = [(k, _p) for k in ("wf1", "bf1", "wf2", "bf2", "wi1", "bi1", "wi2", "bi2")]
@@ -365,6 +370,12 @@ _SIGS = {
                           ctypes.c_int),
     "tsrl_ens_critic_fwd": ([_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64,
                              ctypes.POINTER(EnsNet), _p, _p, _i64, _p, _p], ctypes.c_int),
+    "tsrl_ens_workspace_bytes": ([_i64, _i64, _i64, _i64], ctypes.c_int64),
+    "tsrl_ens_critic_fwd_save": ([_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64,
+                                  ctypes.POINTER(EnsNet), _p, _p, _i64, _p], ctypes.c_int),
+    "tsrl_ens_critic_bwd": ([_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64,
+                             ctypes.POINTER(EnsNet), _p, ctypes.POINTER(EnsGrads), _p, _i64, _p,
+                             _i64, _p], ctypes.c_int),
 }
 
 # tsrl_noisy_weights' descriptor table is a device int64 tensor [n_layers, NOISY_DESC_WORDS]:
@@ -382,6 +393,7 @@ ERR_ENS_SHAPE = 100004        # TSRL_ERR_ENS_SHAPE
 ENS_WIDTHS = (128, 256)       # hidden widths tsrl_ens_critic_fwd takes
 ENS_MAX_IN = 512              # TSRL_ENS_MAX_IN: obs + act columns
 ENS_MAX_MEMBERS = 64          # TSRL_ENS_MAX_MEMBERS
+ENS_MAX_ACT_GRAD = 64         # TSRL_ENS_MAX_ACT_GRAD: act columns tsrl_ens_critic_bwd differentiates
 
 EXPORTED = tuple(_SIGS)
 _LIB = None

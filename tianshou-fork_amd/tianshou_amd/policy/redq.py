@@ -31,12 +31,19 @@ subset of target critics, as one ``tsrl_ens_critic_fwd`` launch (csrc/ensemble.h
 hands ``tsrl_redq_target`` the [subset, b] result with the identity subset.  On the graph leg it
 saves 0.10-0.15 ms per update beyond the run-to-run spread at both bench shapes and both step
 kinds; on the eager leg the medians improve as much but stay inside that leg's spread, hence the
-default (profiles/redq_ensemble_bench.log).  The learn step's three ensemble forwards and its
-backward stay torch's batched GEMMs.
+default (profiles/redq_ensemble_bench.log).
 
-Not built: the ensemble's backward and its learn-step forwards in HIP, widths other than 128 /
-256, fusing the ensemble's H -> 1 head with the loss, bf16 operands, data-parallel REDQ and a
-fused collect step.
+``fused_ensemble_learn`` (on by default; with ``fused``; independent of ``fused_ensemble``): both
+ensemble evaluations of ``_step`` run through ``ensemble_critic(..., learn=...)`` -- the forward
+as ``tsrl_ens_critic_fwd_save`` and the backward as one ``tsrl_ens_critic_bwd``: the critic step
+asks for the six weight gradients (written straight into the flat gradient slots on the eager
+flat path), the actor step for the gradient towards the sampled action alone.  With it a step
+kind is captured into a graph only after one eager step of that kind.  Measured figures and
+the reason for the default: README, REDQ paragraph (profiles/redq_ensemble_learn_bench.log).
+
+Not built: the ensemble's observation gradient, member subsets in the training path, widths other
+than 128 / 256, fusing the ensemble's H -> 1 head with the loss, bf16 operands, data-parallel REDQ
+and a fused collect step.
 """
 from copy import deepcopy
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -198,6 +205,8 @@ class REDQPolicy(_SquashedGaussianMixin, DDPGPolicy):
         self.critic_gradient_step = 0
         self.actor_delay = actor_delay
         self.fused_ensemble = False
+        self.fused_ensemble_learn = True
+        self._stepped_kinds = set()  # the step kinds (do_actor) _step has run
 
     # -- process_fn -----------------------------------------------------------------------------
     def _target_q(self, buffer, indices: np.ndarray) -> torch.Tensor:
@@ -283,6 +292,27 @@ class REDQPolicy(_SquashedGaussianMixin, DDPGPolicy):
         return torch.stack([t.to(torch.float32) for t in losses]), \
             torch.mean(td, dim=0).detach()
 
+    def _graph_ok(self, obs, n: int) -> bool:
+        """With ``fused_ensemble_learn`` a step kind is captured only after one of that kind has
+        run eagerly.  Observed (tools/ddpg_update_bench.py, hidden (256, 256), batch 256, flag
+        on): after the one eager critic-only warm-up update, the capture of the actor-step graph
+        failed inside hipBLASLt with HIP error 900, "operation not permitted when stream is
+        capturing", and the process ended; with one eager actor step before it both captures
+        succeed, as they do with the flag off.  Supposed, not established: hipBLASLt prepares a
+        GEMM form on its first use, and with the flag off the critic's torch backward in the
+        warm-up update is what first uses the forms the actor's backward needs."""
+        if self.fused_ensemble_learn and self._actor_step_due() not in self._stepped_kinds:
+            return False
+        return super()._graph_ok(obs, n)
+
+    def _critics_learn(self, obs, act, learn) -> torch.Tensor:
+        """The ensemble [E, b, 1] inside ``_step``: with ``fused_ensemble_learn`` through the
+        training kernels of csrc/ensemble.hip (``learn`` True: towards the parameters, the
+        critic step; "act": towards the action alone, the actor step), else the torch lines."""
+        if self.fused_ensemble_learn:
+            return ensemble_critic(self.critics, obs, act, learn=learn)
+        return self.critics(obs, act)
+
     def _step(self, fas, obs, act, returns, weight, do_actor: bool, td_out: torch.Tensor,
               loss_out: torch.Tensor, eps: Optional[torch.Tensor] = None) -> None:
         """One update (redq.py:159-191): the ensemble's forward, its fused loss, backward and
@@ -291,13 +321,14 @@ class REDQPolicy(_SquashedGaussianMixin, DDPGPolicy):
         alone and its optimiser pass, then the temperature's optimiser pass and alpha =
         exp(log_alpha) in place; the soft update.  loss_out: critics, actor (, temperature
         loss, alpha)."""
-        q = self.critics(obs, act).flatten(1)
+        self._stepped_kinds.add(bool(do_actor))
+        q = self._critics_learn(obs, act, True).flatten(1)
         handle, _, _ = redq_q_loss(q, returns, weight, td_out, loss_out[:1])
         self._backward_step(handle, ("critics",), fas)
         if do_actor:
             (mu, sigma), _ = self.actor(obs, state=None, info=Batch())
             a, log_prob = sac_sample(mu, sigma, eps)
-            qa = self.critics(obs, a).flatten(1)
+            qa = self._critics_learn(obs, a, "act").flatten(1)
             alpha = self._alpha_tensor(a.device)
             if not self._is_auto_alpha:
                 handle, _, _ = redq_actor_loss(qa, log_prob, alpha, loss_out=loss_out[1:2])

@@ -5,7 +5,8 @@ NoisyLinear's effective parameters, its sigma gradients and the dueling combine 
 of csrc/noisy.hip; ImplicitQuantileNetwork's cosine embedding is tsrl_iqn_embed_fwd / _bwd and
 FractionProposalNetwork's forward tsrl_fqf_propose_fwd (csrc/dqn_dist.hip); ``ensemble_critic``
 evaluates an EnsembleLinear critic, or a subset of its members, as one tsrl_ens_critic_fwd launch
-(csrc/ensemble.hip) where no gradient is recorded."""
+(csrc/ensemble.hip) where no gradient is recorded, and with ``learn`` trains it through
+tsrl_ens_critic_fwd_save / tsrl_ens_critic_bwd."""
 import contextlib
 from ctypes import byref as ctypes_byref
 from typing import Any, Dict, Optional, Sequence, Tuple, Type, Union
@@ -897,24 +898,113 @@ def _ensemble_match(critic: nn.Module, D: int, A: int):
     return l1, l2, l3
 
 
-def ensemble_critic(critic, obs, act, members=None, fused: bool = True) -> torch.Tensor:
+class _EnsShape(Exception):
+    """A training kernel returned TSRL_ERR_ENS_SHAPE: the caller runs the torch lines."""
+
+
+class _EnsembleLearnFn(torch.autograd.Function):
+    """q [E, b, 1] of the ensemble that _ensemble_match opened over x [b, D] and a [b, A] as one
+    tsrl_ens_critic_fwd_save launch; the backward is one tsrl_ens_critic_bwd call that runs only
+    the phases ``needs_input_grad`` asks for: the weight gradients (into the six parameters) and
+    / or the gradient towards ``a``.  x receives none.
+
+    Limitation: ``needs_input_grad`` follows ``requires_grad``, not ``backward(inputs=...)``.  A
+    backward limited to ``a`` over parameters that entered requiring grad still runs the
+    weight-gradient launch, and where fresh flat-bucket slots are published for those parameters
+    (inside ``flat_backward`` of their own optimiser) it makes them their ``.grad``.  A caller
+    that wants the action gradient alone passes the parameters detached, which is what
+    ``ensemble_critic(learn="act")`` does."""
+
+    @staticmethod
+    def forward(ctx, x, a, *weights):
+        (E, _, H), b, D, A = weights[0].shape, len(x), x.shape[1], a.shape[1]
+        lib, dev = _C.lib(), x.device
+        nb = int(lib.tsrl_ens_workspace_bytes(b, H, E, A))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        q = torch.empty((E, b, 1), dtype=torch.float32, device=dev)
+        w = [p.detach() for p in weights]
+        rc = lib.tsrl_ens_critic_fwd_save(
+            _C.ptr_rows(x), x.stride(0), _C.ptr_rows(a), a.stride(0), b, D, A, H, E,
+            ctypes_byref(_C.EnsNet(*(_C.ptr(p) for p in w))), _C.ptr(q), ws.data_ptr(), nb,
+            _C.stream_ptr(dev))
+        if rc == _C.ERR_ENS_SHAPE:
+            raise _EnsShape()
+        _C.check(rc, "tsrl_ens_critic_fwd_save")
+        ctx.save_for_backward(x, a, ws, *w)
+        ctx.params, ctx.nb = weights, nb
+        return q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, a, ws, *w = ctx.saved_tensors
+        want_a, want_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        if not (want_a or want_w):
+            return (None,) * (2 + len(w))
+        (E, _, H), b, D, A = w[0].shape, len(x), x.shape[1], a.shape[1]
+        g = g.reshape(E, b)
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        da = torch.empty((b, A), dtype=torch.float32, device=x.device) if want_a else None
+        grads, direct = None, False
+        if want_w:
+            # eager flat backward: the kernel overwrites every element, so it writes the fresh
+            # flat-bucket slots itself (as _LstmLastFn does) and autograd has nothing to copy
+            slots = [_fresh_grad_slot(p) for p in ctx.params]
+            direct = not torch.is_grad_enabled() and all(s is not None for s in slots)
+            grads = slots if direct else [torch.empty_like(p) for p in w]
+        _C.check(_C.lib().tsrl_ens_critic_bwd(
+            _C.ptr_rows(x), x.stride(0), _C.ptr_rows(a), a.stride(0), b, D, A, H, E,
+            ctypes_byref(_C.EnsNet(*(_C.ptr(p) for p in w))), _C.ptr(g),
+            None if grads is None else ctypes_byref(_C.EnsGrads(*(_C.ptr(t) for t in grads))),
+            _C.ptr(da), A, ws.data_ptr(), ctx.nb, _C.stream_ptr(x.device)),
+            "tsrl_ens_critic_bwd")
+        if direct:
+            for p, s in zip(ctx.params, slots):
+                p.grad = s  # the slot now holds this backward's gradient
+            grads = None
+        return (None, da, *(grads or (None,) * len(w)))
+
+
+def ensemble_critic(critic, obs, act, members=None, fused: bool = True,
+                    learn: Union[bool, str] = False) -> torch.Tensor:
     """``critic(obs, act)`` [E, b, 1] of an ensemble critic, or with ``members`` (a sequence of
     S member indices) ``critic(obs, act)[members]`` [S, b, 1].  Where the critic is the
     EnsembleLinear / ReLU stack that _ensemble_match opens, obs and act are f32 GPU tensors and
     no gradient is being recorded, this is one tsrl_ens_critic_fwd launch that reads obs and act
-    where they lie (no concatenated row) and computes only the members asked for; for anything
-    else -- another activation, a norm layer, another depth, a width the kernel declines, CPU
-    tensors, a recorded gradient, ``fused`` False -- the torch lines run."""
+    where they lie (no concatenated row) and computes only the members asked for.
+
+    ``learn`` (with a recorded gradient, all members, and obs not requiring grad): the forward
+    is tsrl_ens_critic_fwd_save and the backward one tsrl_ens_critic_bwd through
+    ``_EnsembleLearnFn`` -- gradients for the six parameters and for ``act``, none for obs.
+    ``learn="act"`` records the gradient towards ``act`` alone (the parameters enter detached):
+    ``backward(inputs=...)`` does not tell a custom function which inputs it was limited to, so
+    an actor step says here that the weight-gradient phase is not wanted.
+
+    For anything else -- another activation, a norm layer, another depth, a width the kernels
+    decline, an action gradient wider than TSRL_ENS_MAX_ACT_GRAD, CPU tensors, a recorded
+    gradient without ``learn``, ``fused`` False -- the torch lines run."""
     idx = None if members is None else np.ascontiguousarray(
         np.asarray(members).reshape(-1), dtype=np.int32)
     m = None
-    if fused and not torch.is_grad_enabled() and all(
+    train = bool(learn) and torch.is_grad_enabled() and idx is None
+    if fused and (train or not torch.is_grad_enabled()) and all(
             isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2
             for t in (obs, act)) and len(obs) == len(act) > 0:
         x, a = (t.flatten(1) for t in (obs, act))
         x, a = (t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
                 for t in (x, a))
         m = _ensemble_match(critic, x.shape[1], a.shape[1])
+    if m is not None and train:
+        params = [p if learn != "act" else p.detach()
+                  for layer in m for p in (layer.weight, layer.bias)]
+        if not x.requires_grad and (any(p.requires_grad for p in params) or a.requires_grad) \
+                and (not a.requires_grad or 1 <= a.shape[1] <= _C.ENS_MAX_ACT_GRAD):
+            try:
+                return _EnsembleLearnFn.apply(x, a, *params)
+            except _EnsShape:
+                pass
+        m = None
     if m is not None:
         (E, _, H), b = m[0].weight.shape, len(x)
         params = _C.EnsNet(*(_C.ptr(p.detach()) for layer in m for p in (layer.weight, layer.bias)))

@@ -25,6 +25,10 @@ Legs: "graph" (graph_learn=True: the update replayed from captured HIP graphs), 
 (fused=False: the reference's op sequence on the GPU with optim.step() and the per-tensor soft
 update), the torch leg --torch-runs times to show its spread.  --redq-ensemble-ab RUNS: REDQ's
 graph and eager legs RUNS times each with ``fused_ensemble`` on and off, alternating.
+--redq-ensemble-learn-ab RUNS: the same for ``fused_ensemble_learn`` (the learn step's ensemble
+forwards and backward on csrc/ensemble.hip's training kernels), followed by one "ab_summary" line
+per (shape, leg): the medians of the runs' medians per step kind, on and off, and the off leg's
+run-to-run spread (max - min of its runs' medians).
 
 Prints one JSON line per (policy, shape, leg, run)."""
 import argparse
@@ -49,6 +53,8 @@ ap.add_argument("--redq-actor-delay", type=int, default=2)
 ap.add_argument("--redq-ensemble-ab", type=int, default=0, metavar="RUNS",
                 help="REDQ's graph and eager legs RUNS times each with fused_ensemble on and "
                      "off, alternating (on, off, on, ...) in this one process")
+ap.add_argument("--redq-ensemble-learn-ab", type=int, default=0, metavar="RUNS",
+                help="the same for fused_ensemble_learn, with an ab_summary line per leg")
 args = ap.parse_args()
 
 from tianshou_amd.data import Batch, VectorReplayBuffer  # noqa: E402
@@ -177,13 +183,15 @@ for kind in args.policies.split(","):
         buf = fill(cfg)
         for leg in args.legs.split(","):
             variants = [(run, None) for run in range(args.torch_runs if leg == "torch" else 1)]
-            if kind == "redq" and leg != "torch" and args.redq_ensemble_ab:
-                variants = [(run, on) for run in range(args.redq_ensemble_ab)
-                            for on in (True, False)]
+            ab_runs = args.redq_ensemble_learn_ab or args.redq_ensemble_ab
+            ab_attr = "fused_ensemble_learn" if args.redq_ensemble_learn_ab else "fused_ensemble"
+            if kind == "redq" and leg != "torch" and ab_runs:
+                variants = [(run, on) for run in range(ab_runs) for on in (True, False)]
+            medians = {}
             for run, ensemble in variants:
                 policy = make_policy(kind, cfg, leg)
                 if ensemble is not None:
-                    policy.fused_ensemble = ensemble
+                    setattr(policy, ab_attr, ensemble)
                 np.random.seed(0)
                 torch.manual_seed(1)
                 ms, kinds, last = [], [], None
@@ -208,12 +216,20 @@ for kind in args.policies.split(","):
                         len(by["critic"]), len(by["actor"])
                     timing["update_ms_at_delay_20"] = round(
                         (19 * timing["critic_ms_mean"] + timing["actor_ms_mean"]) / 20, 4)
+                    for k in ("critic", "actor"):
+                        medians.setdefault((k, ensemble), []).append(timing[k + "_ms_median"])
                 print(json.dumps({
                     "policy": kind, "config": name, "leg": leg, "run": run,
                     "batch": cfg["batch"], "obs": cfg["D"], "act": cfg["A"],
                     "updates": args.updates, **timing,
-                    **({} if ensemble is None else {"fused_ensemble": ensemble}),
+                    **({} if ensemble is None else {ab_attr: ensemble}),
                     "graphs": len(policy._learn_graphs),
                     "flat_optimiser": bool(policy._flats) and all(
                         policy._flat_ready(n) for n in policy._optim_order),
                     "last": {k: round(float(v), 6) for k, v in last.items()}}), flush=True)
+            if args.redq_ensemble_learn_ab and (("critic", True) in medians):
+                print(json.dumps({"ab_summary": ab_attr, "config": name, "leg": leg, **{
+                    f"{k}_ms_{tag}": round(float(np.median(medians[(k, on)])), 4)
+                    for k in ("critic", "actor") for on, tag in ((True, "on"), (False, "off"))}, **{
+                    f"{k}_ms_off_spread": round(float(np.ptp(medians[(k, False)])), 4)
+                    for k in ("critic", "actor")}}), flush=True)
